@@ -1,7 +1,12 @@
 #!/usr/bin/env python
 """bench.py -- block-sparse matmul hot path on MI355X: effective TFLOP/s (+ GB/s, roofline, CPU baseline).
 
-    python bench.py [--gpus N --steps K --warmup W] [--config headline|cfg2|cfg3]
+    python bench.py [--gpus N --steps K --warmup W] [--config headline|cfg2|cfg3] [--dump-outputs DIR] [--full]
+
+A plain run sets up the timed workload, warms it up, times K steps and prints one JSON line (`value` = effective TFLOP/s,
+`ms_per_step` = milliseconds of one timed step).  `--full` adds everything else the line can carry: the CPU baseline, the other
+densities, configurations and precisions, the attention operators, the sampled parity check against the oracle and, on more than
+one rank, the gradient reduction timed on its own.  `--dump-outputs DIR` writes what the last timed step computed (see dump_outputs).
 
 `--gpus N` with N > 1 spawns the N ranks itself (re-exec under torch.distributed.run, one process per GPU, rendezvous on
 127.0.0.1) unless it already runs under a launcher (WORLD_SIZE set), so both `python bench.py --gpus 8` and the driver's
@@ -128,10 +133,30 @@ def random_layout(CB, KB, density, seed):
     return lay
 
 
+DUMP_BYTES = 60 * 10 ** 6          # --dump-outputs writes at most this much array data in all
+
+
+def dump_outputs(d, named, budget=DUMP_BYTES):
+    """Write each tensor of `named` ({name: tensor}) as d/<name>.npy in float32.  A tensor larger than its share of `budget` is
+    written as a fixed sample of its leading-axis slices (sorted indices drawn by default_rng(0)), so two runs with the same
+    arguments write the same elements."""
+    os.makedirs(d, exist_ok=True)
+    share = budget // len(named)
+    for name, t in named.items():
+        t = t.detach()
+        if t.numel() * 4 > share:
+            if t.dim() < 2 or t[0].numel() * 4 > share:
+                t = t.reshape(-1)
+            k = max(1, share // (t[0].numel() * 4))
+            idx = np.sort(np.random.default_rng(0).choice(t.shape[0], k, replace=False))
+            t = t[idx.tolist()]
+        np.save(os.path.join(d, name + ".npy"), t.float().cpu().numpy())
+
+
 def parse():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
-    p.add_argument("--steps", type=int, default=200)
+    p.add_argument("--steps", type=int, default=200, help="timed steps")
     p.add_argument("--warmup", type=int, default=20)
     p.add_argument("--config", default="headline", choices=["headline", "cfg2", "cfg3"])
     p.add_argument("--prewarm-seconds", type=float, default=0.5,
@@ -146,10 +171,18 @@ def parse():
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-seconds", type=float, default=6.0)
     p.add_argument("--no-attention", action="store_true", help="skip the BASELINE configs[4] (block-sparse attention) extra")
-    p.add_argument("--no-densities", action="store_true", help="skip the 10 % / 50 % runs of the headline metric")
-    p.add_argument("--no-extras", action="store_true", help="headline line only (no fp32 / attention / other densities / CPU baseline)")
+    p.add_argument("--no-densities", action="store_true", help="skip the 10 %% / 50 %% runs of the headline metric")
+    p.add_argument("--no-extras", action="store_true", help="with --full: the headline line only (no fp32 / attention / other densities / CPU baseline)")
     p.add_argument("--master-port", type=int, default=29533)
+    p.add_argument("--full", action="store_true",
+                   help="also run the CPU baseline, the other densities / configurations / precisions, the attention operators, the parity "
+                        "check against the oracle and the gradient reduction on its own (a plain run times the headline workload only)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write y (fprop), dx (bprop) and dw (updat) of the last timed step as DIR/<name>.npy "
+                        "(float32; larger outputs as a fixed, seeded sample of rows, %d MB at most in all)" % (DUMP_BYTES // 10 ** 6))
     a = p.parse_args()
+    if a.steps < 1:
+        p.error("--steps must be at least 1")
     a.bsize_given, a.axis_given, a.dtype_given = a.bsize is not None, a.axis is not None, a.dtype is not None
     return a
 
@@ -454,8 +487,8 @@ def main():
         if world > 1:
             dist.barrier()
 
-    if a.no_extras:
-        a.no_densities = a.no_attention = a.no_cpu_baseline = True
+    if a.no_extras or not a.full:
+        a.no_densities = a.no_attention = a.no_cpu_baseline = a.no_extras = True
     td_of = {"bf16": torch.bfloat16, "f16": torch.float16, "f32": torch.float32}
 
     # ---- CPU legs first: the GPU legs then run to the end of the process (a utilisation sampler next to this run sees them) ----
@@ -514,7 +547,7 @@ def main():
             dx = b.bprop(dy, w)
             if ev: ev[3].record()
             state["i"] = i + 1
-            return y, dx
+            return y, dx, dws[i & 1]
 
         def drain():
             if state["pending"]:
@@ -535,8 +568,9 @@ def main():
         barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for i in range(steps):
+        for i in range(steps - 1):
             step(evs[i])
+        y, dx, dw = step(evs[steps - 1])
         drain()                                            # the last step's gradient belongs to the timed region
         torch.cuda.synchronize()
         barrier()
@@ -548,7 +582,7 @@ def main():
             el = float(t.item())
         per = [float(np.mean([e[i].elapsed_time(e[i + 1]) for e in evs])) for i in range(3)]   # ms: fprop, updat, bprop
         via = red.via if use_dist else None
-        return el, per, via
+        return el, per, via, {"y": y, "dx": dx, "dw": dw}
 
     cus = torch.cuda.get_device_properties(local).multi_processor_count
 
@@ -620,7 +654,10 @@ def main():
         n_local = a.n_local or nloc0
     n_global = n_local * world
     layout, b, w, x, dy = setup(hidden0, bsize0, axis0, dens0, dtype0, n_local)
-    el, per, via = run(b, w, x, dy, a.steps, a.warmup, a.prewarm_seconds)
+    el, per, via, outputs = run(b, w, x, dy, a.steps, a.warmup, a.prewarm_seconds)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, outputs)
+    del outputs
     head = summarize(b, n_local, dtype0, el, per, a.steps, layout)
     dname = "d%d" % round(dens0 * 100)
     workload_name = workload_string(hidden0, bsize0, axis0, dens0, n_local)
@@ -643,9 +680,9 @@ def main():
     }
     if "measured" in head:
         out["measured"] = head["measured"]
-    if rank == 0:
+    if rank == 0 and a.full:
         out.update(parity_check(torch, b, layout, w, x, dy, dtype0))
-    if use_dist:
+    if use_dist and a.full:
         # the gradient reduction on its own (inside the step it overlaps with bprop and the next fprop): time alone, and how much
         # of it the step does not hide
         fused = b.bsize == 32 and b.axis == 1 and dtype0 != "f32"
@@ -693,7 +730,7 @@ def main():
                 continue
             lay2, b2, w2, x2, dy2 = setup(hidden0, bsize0, axis0, d, dtype0, n_local)
             st2 = max(10, a.steps // 2)
-            el2, per2, _ = run(b2, w2, x2, dy2, st2, max(3, a.warmup // 2), min(a.prewarm_seconds, 0.2))
+            el2, per2, _, _ = run(b2, w2, x2, dy2, st2, max(3, a.warmup // 2), min(a.prewarm_seconds, 0.2))
             r = summarize(b2, n_local, dtype0, el2, per2, st2, lay2)
             attach_counters(r, workload_string(hidden0, bsize0, axis0, d, n_local))
             key = "d%d" % round(d * 100)
@@ -709,7 +746,7 @@ def main():
             nl = nl or 4096
             lay2, b2, w2, x2, dy2 = setup(hid, bsz, ax, dn, dt, nl)
             st2 = max(10, a.steps // 4)
-            el2, per2, _ = run(b2, w2, x2, dy2, st2, 5, 0.2)
+            el2, per2, _, _ = run(b2, w2, x2, dy2, st2, 5, 0.2)
             r = summarize(b2, nl, dt, el2, per2, st2, lay2)
             wl = workload_string(hid, bsz, ax, dn, nl)
             attach_counters(r, wl)
@@ -727,7 +764,7 @@ def main():
             wx = (torch.randn(bx.w_shape, device="cuda", generator=gx) * 0.01).to(td)
             xx = (torch.randn(bx.i_shape(nl), device="cuda", generator=gx) * 0.1).to(td)
             dyx = (torch.randn(bx.o_shape(nl), device="cuda", generator=gx) * 0.1).to(td)
-            elx, perx, _ = run(bx, wx, xx, dyx, steps_x, 5, 0.1)
+            elx, perx, _, _ = run(bx, wx, xx, dyx, steps_x, 5, 0.1)
             r = summarize(bx, nl, "bf16", elx, perx, steps_x, layout_x)
             r["workload"] = what
             r.update(parity_check(torch, bx, layout_x, wx, xx, dyx, "bf16"))

@@ -3,7 +3,7 @@
 TEST INFRASTRUCTURE ONLY.  Nothing under blocksparse_amd/ may import this module; only tests/,
 __graft_entry__.smoke() and bench.py's cpu_baseline leg do, and only as the checker.
 
-Pinned: tests/test_bst_oracle_golden.py compares every function here with tests/golden/bst.npz, which
+Pinned: tests/test_bst_oracle_golden.py compares every function here with tests/golden/bst*.npz, which
 tests/golden/make_golden_bst.py produced by running the reference's own NumPy builder / ``*_test`` methods
 (/root/reference/blocksparse/transformer.py) in the authoring container.
 

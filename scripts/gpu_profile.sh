@@ -16,7 +16,7 @@ run_prof() {   # $1 = tag, $2.. = rocprofv3 options ; then -- command
   echo "$DB"
 }
 : > $OUT/status.txt; : > $OUT/pmc.txt
-python $REPO/bench.py > $OUT/bench_line.json 2> $OUT/bench_line.err
+python $REPO/bench.py --full > $OUT/bench_line.json 2> $OUT/bench_line.err
 WORKLOADS=("d10|--density 0.1" "d20|--density 0.2" "d50|--density 0.5" "cfg2|--config cfg2" "cfg3|--config cfg3")
 for W in "${WORKLOADS[@]}"; do
   KEY=${W%%|*}; ARGS=${W#*|}

@@ -1,4 +1,4 @@
-"""Generate tests/golden/bst.npz FROM THE REFERENCE ITSELF (block-sparse attention path, BASELINE configs[4]).
+"""Generate tests/golden/bst*.npz FROM THE REFERENCE ITSELF (block-sparse attention path, BASELINE configs[4]).
 
 Authoring container only (needs /root/reference):    python tests/golden/make_golden_bst.py
 
@@ -163,9 +163,11 @@ def main():
     for k in list(out):
         if k.startswith("math/") and out[k].size > SUB_LIMIT:
             out[k] = sub(out[k])
-    path = os.path.join(HERE, "bst.npz")
-    np.savez_compressed(path, **out)
-    print("wrote", path, os.path.getsize(path) // 1024, "KiB,", len(out), "arrays")
+    sys.path.insert(0, os.path.dirname(HERE))
+    import _golden                                   # split into parts under the size limit of a committed file
+    for f in _golden.save("bst", out, HERE):
+        print("wrote", f, os.path.getsize(os.path.join(HERE, f)) // 1024, "KiB")
+    print(len(out), "arrays")
 
 
 if __name__ == "__main__":

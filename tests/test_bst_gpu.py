@@ -12,6 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, os.path.join(HERE, "golden"))
 import make_golden_bst as G
+import _golden
 from oracle import bst_oracle as O
 from oracle import bsmm_oracle as R          # rounding helpers
 
@@ -87,7 +88,7 @@ def test_against_reference_fixtures(env, case):
     reference's fp32 pathway).  Inputs are fp16-representable, so the only differences are the bf16 storage of
     scores / softmax outputs (2^-9 relative)."""
     torch, BST = env
-    gold = np.load(os.path.join(HERE, "golden", "bst.npz"))
+    gold = _golden.load("bst")
     name, lkey, heads, bsize, hs, batch, cbn, seed = case
     lay = G.layouts()[lkey]
     bst = BST(lay, block_size=bsize, heads=heads, mask_callback=G.CALLBACKS[cbn])

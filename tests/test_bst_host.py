@@ -13,11 +13,12 @@ ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(HERE, "golden"))
 import make_golden_bst as G
+import _golden
 
 
 @pytest.fixture(scope="module")
 def gold():
-    return np.load(os.path.join(HERE, "golden", "bst.npz"))
+    return _golden.load("bst")
 
 
 @pytest.fixture(scope="module")

@@ -9,12 +9,13 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, os.path.join(HERE, "golden"))
 import make_golden_bst as G                                   # case definitions + input generator (no reference import)
+import _golden
 from oracle import bst_oracle as O
 
 
 @pytest.fixture(scope="module")
 def gold():
-    return np.load(os.path.join(HERE, "golden", "bst.npz"))
+    return _golden.load("bst")
 
 
 def _luts(lay, heads):

@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+import _golden
 import _parity as P
 from oracle import bsmm_oracle as orc
 
@@ -365,7 +366,7 @@ def test_identity_init_and_one_mode(env):
 def test_cfg0_golden_on_device(env, golden_dir):
     """BASELINE.json configs[0] (layout=random(128,128), bs 32, N=64, fp32) against the REFERENCE's own outputs."""
     torch, BSMM, _ = env
-    z = np.load(os.path.join(golden_dir, "cfg0_rand128.npz"))
+    z = _golden.load("cfg0_rand128", golden_dir)
     np.random.seed(0)
     layout = np.random.randint(2, size=(128, 128))
     for axis in (0, 1):
@@ -383,9 +384,9 @@ def test_cfg0_golden_on_device(env, golden_dir):
 
 
 def test_golden_math_fixtures_on_device(env, golden_dir):
-    """Every small case of tests/golden/math.npz (outputs of the reference's fprop_test/bprop_test/updat_test)."""
+    """Every small case of the golden `math` fixture (outputs of the reference's fprop_test/bprop_test/updat_test)."""
     torch, BSMM, _ = env
-    z = np.load(os.path.join(golden_dir, "math.npz"))
+    z = _golden.load("math", golden_dir)
     for lay in ("ba16", "holes", "rect", "single"):
         for bs in (8, 16, 32):
             for axis in (0, 1):

@@ -4,6 +4,7 @@ import os
 import numpy as np
 import pytest
 
+import _golden
 from oracle import bsmm_oracle as orc
 
 LUT_CASES = ["rand128", "ba160", "ba160_bs8", "holes", "single", "rect"]
@@ -17,7 +18,7 @@ def luts(golden_dir):
 
 @pytest.fixture(scope="module")
 def math(golden_dir):
-    return np.load(os.path.join(golden_dir, "math.npz"))
+    return _golden.load("math", golden_dir)
 
 
 @pytest.mark.parametrize("name", LUT_CASES)
@@ -82,7 +83,7 @@ def test_oracle_equals_dense(math):
 
 def test_cfg0_random128(golden_dir):
     """BASELINE.json configs[0]: layout=random(128,128) bs 32 N=64 fp32 (host only)."""
-    z = np.load(os.path.join(golden_dir, "cfg0_rand128.npz"))
+    z = _golden.load("cfg0_rand128", golden_dir)
     np.random.seed(0)
     layout = np.random.randint(2, size=(128, 128))
     t = orc.build_layout_luts(layout, 32)
