@@ -176,6 +176,7 @@ inline bool x7_use_list(const bsmm_args* a) {
     return a->axis == 0 && !a->gate;      // (measurement build: the pair kernel wherever it exists)
 #else
     if (a->gate) return false;
+    if (a->plan_inner & 1) return true;      // (doubled tables, header word [14] of the plan: the pair kernel's positional table cannot hold them)
     const double dens = (double)a->blocks / std::max(1.0, (a->C / 16.0) * (a->K / 16.0));
     return a->axis == 0 || dens < 0.4;
 #endif
@@ -1831,7 +1832,7 @@ static bool describe_flat(const int32_t* p, long words, int32_t d[5]) {
         case XCPLAN_MAGIC:   if (p[1] != XCPLAN_VERSION || words < XC_HDR) return false;   d[1] = p[2]; d[2] = p[2]; d[3] = 0; break;
         case X2PLAN_MAGIC:   if (p[1] != X2PLAN_VERSION || words < X2_HDR || p[11] < 2 || p[11] > 4 || p[12] < X2_HDR || words < (long)p[12] + (long)p[3] * X2_G) return false;   d[1] = p[2]; d[2] = p[2]; d[3] = 0; d[4] = p[11]; break;
         case X4PLAN_MAGIC:   if (p[1] != X4PLAN_VERSION || words < X4_HDR || p[2] != X4_G) return false;   d[1] = p[2]; d[2] = p[2]; d[3] = 0; break;
-        case X7PLAN_MAGIC:   if (p[1] != X7PLAN_VERSION || words < X7_HDR || p[12] < X7_HDR || words < (long)p[12] + (long)p[3] * X7_G) return false;   d[1] = p[2]; d[2] = 16; d[3] = 0; break;
+        case X7PLAN_MAGIC:   if (p[1] != X7PLAN_VERSION || words < X7_HDR || p[12] < X7_HDR || words < (long)p[12] + (long)p[3] * X7_G) return false;   d[1] = p[2]; d[2] = 16; d[3] = 0; d[4] = p[14] ? 1 : 0; break;
         case UPLAN_MAGIC:    if (p[1] != UPLAN_VERSION || words < UP_HDR || p[8] < 0 || (p[8] > 0 && (p[8] + U6_HDR > words || p[p[8]] != U6PLAN_MAGIC ||
                                  p[8] + U6_HDR + (long)p[p[8] + 4] * U6_ITEM > words))) return false;
                              d[1] = p[2]; d[2] = p[7]; d[3] = p[4]; d[4] = p[8];               // (plan_inner: word offset of the 'BSU6' section, 0 = none;

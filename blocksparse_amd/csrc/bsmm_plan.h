@@ -255,10 +255,31 @@ constexpr int32_t XCPLAN_VERSION = 1;
 constexpr int XC_G = 8;
 constexpr int XC_HDR = 12;
 
+// Most entries one output block's lists hold for the SAME input block: 1 for the tables of a layout, 2 for the doubled tables of a gated call
+// that runs over two weight images (every entry (c, w) followed by (c, w + blocks), include/bsmm.h bsmm_gate_weights).  Positional tables have
+// ONE slot per (step, output block, input block): a second entry in the same step would take the first one's place and its product be lost.
+inline int xprop_lut_multiplicity(const int32_t* lut, int segments, int n_out_blocks) {
+    std::vector<std::vector<int32_t>> cs((size_t)n_out_blocks);
+    for (int s = 0; s < segments; ++s) {
+        const int32_t off = lut[4 * s], cnt = lut[4 * s + 1], ob = lut[4 * s + 2];
+        if (ob < 0 || ob >= n_out_blocks || cnt < 0) return -1;
+        for (int e = 0; e < cnt; ++e) cs[ob].push_back(lut[2 * (off + e)]);
+    }
+    int most = 1;
+    for (auto& v : cs) {
+        std::sort(v.begin(), v.end());
+        for (size_t i = 0, j = 0; i < v.size(); i = j) {
+            while (j < v.size() && v[j] == v[i]) ++j;
+            most = std::max(most, (int)(j - i));
+        }
+    }
+    return most;
+}
+
 inline long build_xcol_plan(const int32_t* lut, int segments, int blocks, int n_out_blocks, int32_t* out, int G = XC_G) {
     if (!lut || segments <= 0 || blocks <= 0 || n_out_blocks <= 0) return -1;
     const int ngroups = (n_out_blocks + G - 1) / G;
-    struct E { int p, slot, w; };   // slot = 2*wave + half
+    struct E { int p, slot, w, layer; };   // slot = 2*wave + half; layer: see layer_repeats
     std::vector<std::vector<E>> per_group(ngroups);
     for (int s = 0; s < segments; ++s) {
         const int32_t off = lut[4 * s], cnt = lut[4 * s + 1], ob = lut[4 * s + 2];
@@ -266,25 +287,28 @@ inline long build_xcol_plan(const int32_t* lut, int segments, int blocks, int n_
         for (int e = 0; e < cnt; ++e) {
             const int32_t c = lut[2 * (off + e)], w = lut[2 * (off + e) + 1];
             if (w < 0 || w >= blocks || c < 0) return -1;
-            per_group[ob / G].push_back({c >> 1, 2 * (ob % G) + (c & 1), w});
+            per_group[ob / G].push_back({c >> 1, 2 * (ob % G) + (c & 1), w, 0});
         }
     }
     std::vector<int32_t> groups, pairs, wtab;
     for (int g = 0; g < ngroups; ++g) {
         auto& v = per_group[g];
-        std::sort(v.begin(), v.end(), [](const E& a, const E& b) { return a.p != b.p ? a.p < b.p : a.slot < b.slot; });
+        std::stable_sort(v.begin(), v.end(), [](const E& a, const E& b) { return a.p != b.p ? a.p < b.p : a.slot < b.slot; });
+        // the table has ONE entry per (step, wave, half): the k-th entry of a doubled table for the same place gets a step of its own (the same pair again)
+        for (size_t i = 0; i < v.size(); ++i) v[i].layer = (i > 0 && v[i - 1].p == v[i].p && v[i - 1].slot == v[i].slot) ? v[i - 1].layer + 1 : 0;
+        std::stable_sort(v.begin(), v.end(), [](const E& a, const E& b) { return a.p != b.p ? a.p < b.p : (a.layer != b.layer ? a.layer < b.layer : a.slot < b.slot); });
         std::vector<int32_t> gp0;
-        for (auto& e : v) if (gp0.empty() || gp0.back() != e.p) gp0.push_back(e.p);
+        for (size_t i = 0; i < v.size(); ++i) if (i == 0 || v[i - 1].p != v[i].p || v[i - 1].layer != v[i].layer) gp0.push_back(v[i].p);
         const int ns = (int)gp0.size();
         const int step_off = (int)pairs.size();
         // (Starting every group at a different pair, to spread the L2 channels, measured slower: 373 vs 399 TF -- it destroys
         //  the L2 reuse between the groups of one row tile.)
         const std::vector<int32_t>& gp = gp0;
         std::vector<int32_t> tab((size_t)2 * G * ns, -1);
-        int t0 = -1, cur = -1;
-        for (auto& e : v) {
-            if (e.p != cur) { cur = e.p; ++t0; }
-            tab[(size_t)e.slot * ns + t0] = e.w;
+        int t0 = -1;
+        for (size_t i = 0; i < v.size(); ++i) {
+            if (i == 0 || v[i - 1].p != v[i].p || v[i - 1].layer != v[i].layer) ++t0;
+            tab[(size_t)v[i].slot * ns + t0] = v[i].w;
         }
         pairs.insert(pairs.end(), gp.begin(), gp.end());
         wtab.insert(wtab.end(), tab.begin(), tab.end());
@@ -388,7 +412,7 @@ inline long build_xcol2_plan(const int32_t* lut, int segments, int blocks, int n
     std::vector<std::array<int32_t, X2_G>> gcols(ngroups);
     for (auto& c : gcols) c.fill(-1);
     for (int ob = 0; ob < n_out_blocks; ++ob) gcols[grp_of[ob]][wave_of[ob]] = ob;
-    struct E { int p, wave, half, w; };
+    struct E { int p, wave, half, w, layer; };
     std::vector<std::vector<E>> per_group(ngroups);
     for (int s = 0; s < segments; ++s) {
         const int32_t off = lut[4 * s], cnt = lut[4 * s + 1], ob = lut[4 * s + 2];
@@ -397,15 +421,21 @@ inline long build_xcol2_plan(const int32_t* lut, int segments, int blocks, int n
             const int32_t c = lut[2 * (off + e)], w = lut[2 * (off + e) + 1];
             if (w < 0 || w >= blocks || c < 0) return -1;
             if (c >= 2 * 0xffff) return 0;
-            per_group[grp_of[ob]].push_back({c >> 1, wave_of[ob], c & 1, w});
+            per_group[grp_of[ob]].push_back({c >> 1, wave_of[ob], c & 1, w, 0});
         }
     }
     // steps per phase from the mean number of blocks per (group, pair) step, with 30 % headroom for the spread
     size_t nsteps_all = 0;
     for (int g = 0; g < ngroups; ++g) {
         auto& v = per_group[g];
-        std::sort(v.begin(), v.end(), [](const E& a, const E& b) { return a.p != b.p ? a.p < b.p : (a.wave != b.wave ? a.wave < b.wave : a.half < b.half); });
-        for (size_t i = 0; i < v.size(); ++i) nsteps_all += (i == 0 || v[i].p != v[i - 1].p);
+        std::stable_sort(v.begin(), v.end(), [](const E& a, const E& b) { return a.p != b.p ? a.p < b.p : (a.wave != b.wave ? a.wave < b.wave : a.half < b.half); });
+        // ONE slot byte per (step, wave, half): the k-th entry a doubled table (two weight images, include/bsmm.h bsmm_gate_weights) has for the same
+        // place goes into a step of its own -- the same pair again, as for a pair with more blocks than WCAP
+        for (size_t i = 0; i < v.size(); ++i)
+            v[i].layer = (i > 0 && v[i - 1].p == v[i].p && v[i - 1].wave == v[i].wave && v[i - 1].half == v[i].half) ? v[i - 1].layer + 1 : 0;
+        std::stable_sort(v.begin(), v.end(), [](const E& a, const E& b) {
+            return a.p != b.p ? a.p < b.p : (a.layer != b.layer ? a.layer < b.layer : (a.wave != b.wave ? a.wave < b.wave : a.half < b.half)); });
+        for (size_t i = 0; i < v.size(); ++i) nsteps_all += (i == 0 || v[i].p != v[i - 1].p || v[i].layer != v[i - 1].layer);
     }
     const double mean = nsteps_all ? (double)blocks / (double)nsteps_all : 0.0;
     int PH = force_ph;
@@ -415,12 +445,12 @@ inline long build_xcol2_plan(const int32_t* lut, int segments, int blocks, int n
     int max_ph = 0;
     for (int g = 0; g < ngroups; ++g) {
         auto& v = per_group[g];
-        // steps: runs of equal pair, at most WCAP entries each (a wave's two halves stay in one step)
+        // steps: runs of equal (pair, layer), at most WCAP entries each (a wave's two halves stay in one step)
         struct Step { int p; size_t lo, hi; };
         std::vector<Step> steps;
         for (size_t i = 0; i < v.size();) {
             size_t j = i;
-            while (j < v.size() && v[j].p == v[i].p) ++j;
+            while (j < v.size() && v[j].p == v[i].p && v[j].layer == v[i].layer) ++j;
             size_t lo = i;
             while (lo < j) {
                 size_t hi = std::min(j, lo + WCAP);
@@ -768,6 +798,7 @@ inline long build_xflow_plan(const int32_t* lut, int segments, int blocks, int n
 // Layout (int32): [0] magic 'BSX7' [1] version [2] X7_G [3] ngroups [4] nphases_total [5] off_groups [6] off_px
 //                 [7] off_tab (multiple of 4) [8] n_out_blocks [9] X7_WCAP [10] max phases of a group [11] off_lists
 //                 [12] off_cols: cols[ngroups][32] = the output block of every (group, column position), -1 = none (version 3)  [13] 1 if regrouped
+//                 [14] 1 if the table names an (output block, input block) twice (doubled tables): only the list section is complete then
 //   groups[ngroups][4] = (phase_off, nphases, first_out_block, n_out_blocks_in_group)
 //   px [nphases_total]           quad of step 0 | quad of step 1 << 16   (0xffff = no such step)
 //   tab[nphases_total][16][12]   per phase and wave:
@@ -797,6 +828,12 @@ constexpr int X7_PHW = 16 * X7_LIST + 128;   // words of a phase in the list sec
 inline long build_xcol16s_plan(const int32_t* lut, int segments, int blocks, int n_out_blocks, int32_t* out, bool regroup = true) {
     if (!lut || segments <= 0 || blocks <= 0 || n_out_blocks <= 0) return -1;
     if (blocks >= (1 << 23)) return 0;                                       // 32-bit byte offsets into W
+    // doubled tables (two entries per (output block, input block)): the LIST section holds them -- a wave's list has room for 16 entries, so a phase
+    // takes a second step only where every wave's entries still fit -- the positional section cannot (header word [14] = 1: the list kernel only)
+    const int mult = xprop_lut_multiplicity(lut, segments, n_out_blocks);
+    if (mult < 0) return -1;
+    if (mult > 2) return 0;
+    const bool repeats = mult == 2;
     const int G = X7_G, ngroups = (n_out_blocks + G - 1) / G;
     std::vector<int> grp_of, pos_of;                      // (round 6: unbalanced layouts are regrouped, regroup_output_blocks)
     const bool regrouped = regroup_output_blocks(lut, segments, n_out_blocks, G, !regroup, grp_of, pos_of);
@@ -832,7 +869,11 @@ inline long build_xcol16s_plan(const int32_t* lut, int segments, int blocks, int
         const int phase_off = (int)px.size();
         for (size_t s = 0; s < steps.size();) {
             const size_t n0 = steps[s].hi - steps[s].lo;
-            const bool two = s + 1 < steps.size() && n0 + (steps[s + 1].hi - steps[s + 1].lo) <= (size_t)X7_WCAP;
+            bool two = s + 1 < steps.size() && n0 + (steps[s + 1].hi - steps[s + 1].lo) <= (size_t)X7_WCAP;
+            if (two && repeats) {                    // (without repeats a wave has at most 2 steps x 2 columns x 4 input blocks = 16 entries)
+                int per_wave[16] = {0};
+                for (size_t i = steps[s].lo; i < steps[s + 1].hi; ++i) two = two && ++per_wave[v[i].col >> 1] <= 16;
+            }
             const int nst = two ? 2 : 1;
             px.push_back(steps[s].p | ((two ? steps[s + 1].p : 0xffff) << 16));
             std::vector<int32_t> row((size_t)16 * X7_ROW, 0);
@@ -914,7 +955,7 @@ inline long build_xcol16s_plan(const int32_t* lut, int segments, int blocks, int
     if (out) {
         std::fill(out, out + off_tab, 0);
         const int32_t hdr[X7_HDR] = {X7PLAN_MAGIC, X7PLAN_VERSION, G, ngroups, (int32_t)px.size(), off_groups, off_px, off_tab,
-                                     n_out_blocks, X7_WCAP, max_ph, (int32_t)off_lists, (int32_t)off_cols, regrouped ? 1 : 0, 0, 0};
+                                     n_out_blocks, X7_WCAP, max_ph, (int32_t)off_lists, (int32_t)off_cols, regrouped ? 1 : 0, repeats ? 1 : 0, 0};
         std::copy(hdr, hdr + X7_HDR, out);
         std::copy(groups.begin(), groups.end(), out + off_groups);
         std::copy(px.begin(), px.end(), out + off_px);

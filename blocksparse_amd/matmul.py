@@ -371,7 +371,7 @@ class BlocksparseMatMul(object):
         prepares on every call."""
         lib = _lib.load()
         need = lib.bsmm_prepared_bytes(op, ctypes.byref(a))
-        if not need:
+        if not need or w.data_ptr() % 16:      # (weights that are not 16-byte aligned: the library runs the V_FMA kernel, which takes no prepared pieces)
             return
         key = (op, w.data_ptr(), w._version, a.stream)
         hit = self._prepared_w.get(op)

@@ -218,7 +218,10 @@ int bsmm_gate_grad(void* dw_out, float* dg, const void* dw, const void* W, const
  *   out[0][w] = round(gate[w] * W[w]),   pieces == 2:  out[1][w] = round(gate[w] * W[w] - out[0][w])      (gate 0: zeros)
  * out: [pieces][blocks][bsize][bsize] of the storage type (16-bit types only).  A 0 / 1 gate (pruning mask) needs ONE piece and the
  * ungated call over `out` is exact; any other gate takes both pieces and the ungated call over the DOUBLED lookup table (every entry (c, w)
- * followed by (c, w + blocks); blocks' = 2 * blocks): the sum is g * w to ~2^-17.  blocksparse_amd/matmul.py composes the two. */
+ * followed by (c, w + blocks); blocks' = 2 * blocks): the sum is g * w to ~2^-17.  blocksparse_amd/matmul.py composes the two.
+ * Plans for a doubled table: the flow kernel ('BSX4') and the bsize-16 list kernel ('BSX7', header word [14] = 1: never its pair kernel) walk
+ * entry lists; the positional plans ('BSX2', 'BSXC': one slot per (step, output block, input block)) give the second image of a block a step
+ * of its own over the same pair of input blocks. */
 int bsmm_gate_weights(const void* W, const float* gate, void* out, int32_t blocks, int32_t bsize, int32_t dtype, int32_t pieces,
                       void* stream);
 

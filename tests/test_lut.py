@@ -79,7 +79,8 @@ def test_big_layout_builds_fast():
 
 def test_double_tables_for_gated_calls():
     """lut.double_tables (round 6: gated calls on the ungated kernels over hi / lo weight images): every entry (c, w) is followed by
-    (c, w + blocks), headers keep their order, lengths and offsets double, and the doubled table is a valid xprop table for every plan builder."""
+    (c, w + blocks), headers keep their order, lengths and offsets double, and the doubled table is a valid xprop table for every plan builder (the bsize-16 list
+    plan holds both images of every block; the GPU tier runs the kernels over such plans against the oracle)."""
     import ctypes
     from blocksparse_amd import _lib as lib
     from blocksparse_amd.matmul import _host_plan
@@ -104,5 +105,22 @@ def test_double_tables_for_gated_calls():
                 eb = lb[2 * off2:2 * (off2 + cnt2)].reshape(-1, 2, 2)
                 assert np.array_equal(eb[:, 0, :], ea) and np.array_equal(eb[:, 1, 0], ea[:, 0]) and np.array_equal(eb[:, 1, 1], ea[:, 1] + B)
             if not segmented:
-                for bs, axis, opt in ((32, 1, lib.PLAN_XCOL_FLOW), (32, 0, 0), (16, 0, 0), (16, 1, 0)):
+                for bs, axis, opt in ((32, 1, lib.PLAN_XCOL_FLOW), (32, 0, 0), (32, 1, 0), (32, 1, lib.PLAN_XCOL_UNSTAGED), (16, 0, 0), (16, 1, 0)):
                     assert _host_plan(b["lut"], S, 2 * B, n_out, bs, lib.BF16, axis, opt) is not None
+                # 'BSX7' (bsize 16, csrc/bsmm_plan.h): header word [14] = 1 marks the repeats (the list kernel only), and the list section -- per phase
+                # 16 wave lists of X7_LIST words (word 38: entry counts of the wave's two columns), then 128 words of requests (pairs of weight-block
+                # byte offsets, word 97: how many pairs) -- fetches every image of every block and keeps a wave within its 16 entries
+                X7_MAGIC, X7_LIST, X7_REQ, X7_NPAIRS, X7_COUNTS, X7_BLOCK_BYTES = 0x42535837, 40, 128, 97, 38, 512
+                for axis in (0, 1):
+                    plain, dbl = (_host_plan(x["lut"], S, nb, n_out, 16, lib.BF16, axis, 0) for x, nb in ((a, B), (b, 2 * B)))
+                    assert plain[0] == dbl[0] == X7_MAGIC and plain[14] == 0 and dbl[14] == 1
+                    seen, per_wave = set(), 0
+                    for ph in range(int(dbl[4])):
+                        base = int(dbl[11]) + ph * (16 * X7_LIST + X7_REQ)
+                        req = dbl[base + 16 * X7_LIST:base + 16 * X7_LIST + X7_REQ]
+                        for k in range(int(req[X7_NPAIRS])):
+                            seen.update((int(req[2 * k]) // X7_BLOCK_BYTES, int(req[2 * k + 1]) // X7_BLOCK_BYTES))
+                        for wv in range(16):
+                            cnt = int(dbl[base + X7_LIST * wv + X7_COUNTS])
+                            per_wave = max(per_wave, (cnt & 255) + ((cnt >> 8) & 255))
+                    assert seen == set(range(2 * B)) and per_wave <= 16
