@@ -5,5 +5,7 @@ from .matmul import BlocksparseMatMul  # noqa: F401
 from .transformer import BlocksparseTransformer  # noqa: F401
 from .sparse_proj import SparseProj  # noqa: F401
 from . import checkpoint  # noqa: F401
+from . import sparsity  # noqa: F401
+from .sparsity import blocksparse_norm, blocksparse_l2_decay, blocksparse_prune  # noqa: F401
 
 __version__ = "0.1.0"

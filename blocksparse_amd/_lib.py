@@ -43,6 +43,9 @@ SYMBOLS = ("bsmm_fprop", "bsmm_bprop", "bsmm_updat", "bsmm_updat_finalize", "bsm
 DIST_SYMBOLS = ("bsmm_dist_unique_id", "bsmm_dist_create", "bsmm_dist_allreduce_begin", "bsmm_dist_allreduce_end", "bsmm_dist_stream",
                 "bsmm_dist_world", "bsmm_dist_destroy", "bsmm_dist_dw_shard_elems", "bsmm_dist_dw_layout", "bsmm_dist_dw_begin", "bsmm_dist_dw_emulate",
                 "bsmm_dist_dw_end")
+SPARSITY_SYMBOLS = ("bsmm_block_norm", "bsmm_block_l2_decay", "bsmm_block_threshold_prune", "bsmm_block_prune", "bsmm_feature_reduce",
+                    "bsmm_reduced_dw", "bsmm_reduced_dw_workspace_bytes")      # include/bsmm_sparsity.h
+NORM_MAX, NORM_L2 = 0, 1
 BST_SYMBOLS = ("bst_nt", "bst_nn", "bst_tn", "bst_masked_softmax", "bst_softmax_grad", "bst_partial_autoregressive_mask", "bst_nt_softmax", "bst_nt_softmax_grad")
 
 
@@ -201,6 +204,17 @@ def load():
     lib.bst_softmax_grad.restype = ctypes.c_int
     lib.bst_partial_autoregressive_mask.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
     lib.bst_partial_autoregressive_mask.restype = ctypes.c_int
+    # include/bsmm_sparsity.h
+    lib.bsmm_block_norm.argtypes = [vp, vp, i32, i32, i32, i32, vp]
+    lib.bsmm_block_l2_decay.argtypes = [vp, vp, f32, f32, i32, i32, i32, vp]
+    lib.bsmm_block_threshold_prune.argtypes = [vp, vp, f32, i32, i32, i32, i32, vp]
+    lib.bsmm_block_prune.argtypes = [vp, vp, i32, i32, vp]
+    lib.bsmm_feature_reduce.argtypes = [ctypes.POINTER(vp), i32, vp, i32, i32, i32, i32, i32, i32, vp]
+    lib.bsmm_reduced_dw.argtypes = [vp, vp, vp, i32, i32, i32, f32, i32, i32, vp, ctypes.c_size_t, vp]
+    for name in SPARSITY_SYMBOLS:
+        getattr(lib, name).restype = ctypes.c_int
+    lib.bsmm_reduced_dw_workspace_bytes.argtypes = [i32, i32, i32]
+    lib.bsmm_reduced_dw_workspace_bytes.restype = ctypes.c_size_t
     if lib.bsmm_version() != ABI_VERSION:
         raise RuntimeError("blocksparse_amd: %s reports ABI version %d, this binding expects %d -- rebuild the library "
                            "(python -c 'import __graft_entry__ as g; g.build()')" % (LIB_PATH, lib.bsmm_version(), ABI_VERSION))

@@ -768,6 +768,33 @@ class BlocksparseMatMul(object):
         new_gate = torch.ones(n, dtype=gate.dtype, device=gate.device) if is_t else np.ones((n,), dtype=gate_np.dtype)
         return param, new_gate
 
+    # ---- dynamic sparsity (blocksparse_amd/sparsity.py) --------------------------------------------
+    def block_reduced_full_dw(self, xs, dys, scale=1.0, norm="max", dw_full=None, return_reduced=False, exact=False):
+        """Growth score for EVERY block of the dense CB x KB grid, fp32 [CB, KB] ("block reduced full param gradient for use in network
+        growth", blocksparse/matmul.py:556-609, op BlocksparseReducedDW):  scale * x_red . y_red^T, where x_red / y_red hold, per minibatch
+        column, the max-abs (``norm="max"``) or l2 norm (``"l2"``) over the features of each block of ``xs`` / ``dys`` (equally long lists
+        of activations in this operator's layout).  It is an upper bound of the block's norm in the dense weight gradient, not an estimate.
+        More than 8 pairs run in groups of 8, each accumulating onto the previous result; ``dw_full`` (fp32 [CB, KB]) is accumulated onto
+        in place; ``scale == 0`` computes nothing.  ``return_reduced=True`` (at most 8 pairs): (dw, x_reduced, y_reduced) with the reduced
+        arrays in the reference's shapes, [feature blocks, pairs, N] on feature axis 0 and [pairs, N, feature blocks] on axis 1 (16-bit:
+        the activations' type, bf16 for fp32 activations).
+        ``exact=True``: the true per-block norm of the dense gradient instead -- the weight gradient (``updat``) of a cached twin of this
+        operator over the all-ones layout, then ``blocksparse_norm``, scattered to [CB, KB].  The norms are always taken of an fp32
+        gradient: the fp32 sums of the streaming weight-gradient kernel (``updat(sums_only=True)``) where it serves the configuration
+        (bsize 32 / 64: 16-bit types, and fp32 with one pair on feature axis 1), else the fp32 weight gradient of fp32 copies of the
+        activations -- never of a gradient rounded to a 16-bit type, whose max norm alone would be off by up to 2^-9 per block.
+        ``scale`` and ``dw_full`` apply alike."""
+        from . import sparsity
+        return sparsity.block_reduced_full_dw(self, xs, dys, scale=scale, norm=norm, dw_full=dw_full, return_reduced=return_reduced, exact=exact)
+
+    def relayout(self, param, new_layout, init=0.0):
+        """(new_bsmm, new_param): this operator's block size, feature axis and ``z_order`` over ``new_layout``, with the weights carried
+        over -- a block present in both layouts is copied to its new index (block ids mapped through the two ``updat_list``s, one
+        ``index_copy_`` on the device), new blocks are filled with ``init``, dropped blocks are gone.  Closes the loop: score, pick blocks,
+        new layout, carry the weights over."""
+        from . import sparsity
+        return sparsity.relayout(self, param, new_layout, init=init)
+
     def matmul(self, I, W, gate=None, gate_grad=False, dw_gated=False, name=None, bench=0):
         return self.__call__(I, W, gate=gate, gate_grad=gate_grad, dw_gated=dw_gated, name=name, bench=bench)
 
