@@ -38,6 +38,15 @@ except Exception:  # pragma: no cover
     torch = None
 
 
+def _capturing():
+    """True while torch's current stream is being captured into a graph.  (A process without a device -- the host-only tier -- cannot be
+    capturing: the query itself raises there.)"""
+    try:
+        return bool(torch.cuda.is_current_stream_capturing())
+    except RuntimeError:
+        return False
+
+
 def _dtype_code(dt):
     if dt == torch.float32:
         return _lib.F32
@@ -232,18 +241,24 @@ class BlocksparseMatMul(object):
         return entry is not None and entry[0]() is w and entry[1] == key
 
     def invalidate_weights(self):
-        """Forget every per-weights image (prepared pieces, quadrant views).  Needed only after a mutation PyTorch's version counter
-        cannot see (``w.data.add_()``, a raw-pointer write, another library writing into the storage)."""
+        """Forget everything derived from the CONTENTS of a tensor: the per-weights images (prepared pieces, quadrant views) and the
+        binary / general verdict on a gate, also those of the quadrant operator (bsize 64) and of the doubled-table operator of gated calls.
+        Needed only after a mutation PyTorch's version counter cannot see (``w.data.add_()``, ``gate.data.copy_()``, a raw-pointer write,
+        another library writing into the storage).  A captured graph needs no call: a capture neither reads nor fills these caches."""
         self._prepared_w.clear()
         self._split64_hit = None
-        if self._inner is not None:
-            self._inner.invalidate_weights()
+        self._gate_kind_hit = None
+        for other in (self._inner, self._dbl):
+            if other is not None:
+                other.invalidate_weights()
 
     def _split64_cached(self, w):
         """The quadrant view of a weight tensor for fprop / bprop, made once per (tensor object, version): W is constant across the
         calls of a pass; an in-place update (``w._version``) or ANOTHER tensor (even at the same address: the entry holds a weak
         reference and compares identity) invalidates it.  Not used under autograd (the gather is part of the graph there)."""
         if w.requires_grad and torch.is_grad_enabled():
+            return self._split64(w)
+        if _capturing():      # the gather becomes part of the graph (a replay sees the weights of that moment); the cache is neither read nor filled
             return self._split64(w)
         key = (w.data_ptr(), w._version, w.dtype, w.device)
         if not self._same_weights(self._split64_hit, w, key):
@@ -368,11 +383,20 @@ class BlocksparseMatMul(object):
         reference to ``w`` and compares identity: a temporary (``w_master.to(bf16)``, ``W * mask``, an ``l2_normalize`` output) that the
         allocator places at a freed tensor's address with the same version is a different object and is prepared again.
         A mutation the version counter cannot see (``w.data.add_()``) needs ``invalidate_weights()``; ``cache_prepared = False``
-        prepares on every call."""
+        prepares on every call.
+
+        Under stream capture the cache is neither read nor filled: a hit would leave the preparation out of the graph (a replay after an
+        optimizer step would multiply with the old pieces), a stored entry would describe work that was recorded, not run.  The pieces are
+        made inside the capture, into a buffer of the graph's own pool; the caller holds the returned buffer until its launch is recorded."""
         lib = _lib.load()
         need = lib.bsmm_prepared_bytes(op, ctypes.byref(a))
         if not need or w.data_ptr() % 16:      # (weights that are not 16-byte aligned: the library runs the V_FMA kernel, which takes no prepared pieces)
-            return
+            return None
+        if _capturing():
+            buf = torch.empty(need, dtype=torch.uint8, device=w.device)
+            _lib.check(lib.bsmm_prepare_weights(op, w.data_ptr(), buf.data_ptr(), ctypes.byref(a)), "bsmm_prepare_weights")
+            a.prepared_w = buf.data_ptr()
+            return buf
         key = (op, w.data_ptr(), w._version, a.stream)
         hit = self._prepared_w.get(op)
         if not (self.cache_prepared and self._same_weights(hit, w, key)):
@@ -380,6 +404,7 @@ class BlocksparseMatMul(object):
             _lib.check(lib.bsmm_prepare_weights(op, w.data_ptr(), buf.data_ptr(), ctypes.byref(a)), "bsmm_prepare_weights")
             hit = self._prepared_w[op] = (weakref.ref(w), key, buf)
         a.prepared_w = hit[2].data_ptr()
+        return hit[2]
 
     def _out_shape(self, x, feat_out):
         shp = list(x.shape)
@@ -405,16 +430,18 @@ class BlocksparseMatMul(object):
 
     def _gate_kind_of(self, gate):
         """"binary" (every gate 0 or 1: a pruning mask -- ONE exact weight image) or "general" (two images, g w to ~2^-17).  Looked at once
-        per (tensor object, version): one host sync the first time a gate (or a changed gate) is seen, none afterwards; under stream capture
-        an unseen gate counts as "general" (always correct).  ``gate_kind = "binary" / "general"`` is the caller's promise instead."""
+        per (tensor object, version): one host sync the first time a gate (or a changed gate) is seen, none afterwards.  Under stream capture
+        EVERY gate counts as "general" (always correct) and nothing is stored: a verdict on the gate's contents at capture time, cached or
+        not, would be baked into a graph whose replays read whatever the gate buffer holds by then.  ``gate_kind = "binary" / "general"`` is
+        the caller's promise instead, under capture too; a mutation the version counter cannot see needs ``invalidate_weights()``."""
         if self.gate_kind != "auto":
             return self.gate_kind
+        if _capturing():
+            return "general"
         key = (gate.data_ptr(), gate._version)
         hit = self._gate_kind_hit
         if hit is not None and hit[0]() is gate and hit[1] == key:
             return hit[2]
-        if torch.cuda.is_current_stream_capturing():
-            return "general"
         kind = "binary" if bool(((gate == 0) | (gate == 1)).all().item()) else "general"
         self._gate_kind_hit = (weakref.ref(gate), key, kind)
         return kind
@@ -493,7 +520,7 @@ class BlocksparseMatMul(object):
         a.gate = gate.data_ptr() if gate is not None else None
         if need_prep:
             a.prepared_w = None
-            self._prepared(a, _lib.OP_FPROP, w)
+            held = self._prepared(a, _lib.OP_FPROP, w)      # (held until the launch below is on the stream)
             self._workspace(a, _lib.OP_FPROP, x.device)
         _lib.check(lib.bsmm_fprop(x.data_ptr(), w.data_ptr(), y.data_ptr(), ctypes.byref(a)), "bsmm_fprop")
         return y
@@ -520,7 +547,7 @@ class BlocksparseMatMul(object):
         a.gate = gate.data_ptr() if gate is not None else None
         if need_prep:
             a.prepared_w = None
-            self._prepared(a, _lib.OP_BPROP, w)
+            held = self._prepared(a, _lib.OP_BPROP, w)      # (held until the launch below is on the stream)
             self._workspace(a, _lib.OP_BPROP, dy.device)
         _lib.check(lib.bsmm_bprop(dy.data_ptr(), w.data_ptr(), dx.data_ptr(), ctypes.byref(a)), "bsmm_bprop")
         return dx

@@ -279,9 +279,11 @@ class BlocksparseTransformer(object):
     def query_key_softmax(self, q, k, scale=1.0, autoregress_at_key=None, dtype=None):
         """``masked_softmax(query_key_op(q, k), scale, autoregress_at_key, dtype)`` as one operator (round 6): where the fused kernel serves the
         configuration (block size 32, head states of 32 / 64 / 128, query rows of up to 20 blocks) the raw scores never reach memory -- one
-        launch, a third of the bytes; elsewhere the two operators run as the reference composes them (blocksparse/transformer.py:364-409).  Same
-        values either way (the scores are rounded to the score type before the softmax in both), same gradients (blocksparse_softmax_grad, then
-        blocksparse_transformer_nt_grad)."""
+        launch, a third of the bytes; elsewhere ``bst_nt`` and ``bst_masked_softmax`` run one after the other.  Same values either way: the raw
+        scores are rounded to ``_score_dtype(q.dtype)`` (fp16 next to fp16 activations, bf16 otherwise) before the softmax in both, with the
+        default ``dtype``; same gradients (blocksparse_softmax_grad, then blocksparse_transformer_nt_grad).  ``query_key_op`` keeps the
+        reference's bf16 scores (blocksparse/transformer.py:364-409), so ``masked_softmax(query_key_op(q, k))`` gives these values for fp32 and
+        bf16 activations only: next to fp16 activations its scores carry 8 bits where these carry 11."""
         self.softmax_dtype = self._score_dtype(q.dtype)
         if self.softmax_mask is None:
             if autoregress_at_key is not None:
@@ -301,8 +303,11 @@ class BlocksparseTransformer(object):
     def attention(self, q, k, v, scale=1.0, autoregress_at_key=None):
         """``weight_value_op(masked_softmax(query_key_op(q, k), scale, autoregress_at_key), v)`` as one operator (round 6): two launches forward
         (scores + softmax, weighted values) and four backward (dv; [scores of (dy, v) + softmax gradient] as one; dq; dk) where the fused kernels
-        serve the configuration, the reference's composition elsewhere.  The probabilities are kept for the backward pass, the raw scores and
-        the gradient of the probabilities never reach memory."""
+        serve the configuration, the same three steps as separate launches elsewhere -- same values and gradients either way: raw scores (and, in the
+        backward pass, the scores of (dy, v)) are rounded to ``_score_dtype(q.dtype)`` in both.  That is the composition of the three operators
+        for fp32 and bf16 activations; next to fp16 activations ``query_key_op`` rounds its scores to bf16 and the composition differs by that
+        rounding.  On the fused path the probabilities are kept for the backward pass, the raw scores and the gradient of the probabilities
+        never reach memory."""
         self.softmax_dtype = self._score_dtype(q.dtype)
         if self.softmax_mask is None:
             if autoregress_at_key is not None:
@@ -435,7 +440,7 @@ if torch is not None:
             q, k = q.contiguous(), k.contiguous()
             y = bst._nt_softmax(q, k, scale, mask_t, y_dtype)
             if y is None:
-                y = bst._softmax_fwd(bst._nt(q, k, torch.bfloat16), scale, mask_t, y_dtype)
+                y = bst._softmax_fwd(bst._nt(q, k, bst._score_dtype(q.dtype)), scale, mask_t, y_dtype)      # (the fused kernel's rounding of the raw scores)
             ctx.bst, ctx.scale = bst, scale
             ctx.save_for_backward(q, k, y)
             return y
@@ -458,7 +463,7 @@ if torch is not None:
             q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
             a = bst._nt_softmax(q, k, scale, mask_t, a_dtype)
             if a is None:
-                a = bst._softmax_fwd(bst._nt(q, k, torch.bfloat16), scale, mask_t, a_dtype)
+                a = bst._softmax_fwd(bst._nt(q, k, bst._score_dtype(q.dtype)), scale, mask_t, a_dtype)
             ctx.bst, ctx.scale = bst, scale
             ctx.save_for_backward(q, k, v, a)
             return bst._xn(a, v, False)
@@ -471,7 +476,7 @@ if torch is not None:
             dv = bst._xn(a, dy, True)
             dx = bst._nt_softmax_grad(dy, v, a, ctx.scale)
             if dx is None:
-                dx = bst._softmax_bwd(bst._nt(dy, v, a.dtype), a, ctx.scale)
+                dx = bst._softmax_bwd(bst._nt(dy, v, bst._score_dtype(q.dtype)), a, ctx.scale)
             dq = bst._xn(dx, k, False)
             dk = bst._xn(dx, q, True)
             return None, dq, dk, dv, None, None, None

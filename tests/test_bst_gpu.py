@@ -377,3 +377,83 @@ def test_attention_operator_matches_the_composed_operators(env):
     y = bst64.attention(q, k, v, scale=0.125)
     y.sum().backward()
     assert torch.isfinite(y).all() and torch.isfinite(q.grad).all() and torch.isfinite(k.grad).all() and torch.isfinite(v.grad).all()
+
+
+# ---- fp16 activations: one rounding of the raw scores, whichever path serves the layout ---------------------------------------
+def _fp16_case(lay, heads, hs, batch, seed, act):
+    """Inputs of the reference generator with Q and K doubled (std of scale * scores ~ 1.3: at the generator's own amplitude the bf16 and the
+    fp16 rounding of the scores give probabilities 7e-4 apart, inside the 1e-3 bar -- no L2 test would see which one ran)."""
+    lay = np.asarray(lay)
+    blocks = int((lay if lay.ndim == 3 else lay[None])[0].sum())
+    inp = G.gen_inputs(lay, heads, 32, hs, batch, blocks, seed)
+    rq = lambda a: R.round_to(a, act)
+    return rq(2.0 * inp["Q"]), rq(2.0 * inp["K"]), rq(inp["V"]), rq(inp["E"])
+
+
+@pytest.mark.parametrize("shape,hs", [((1, 2, 21), 64), ((1, 3, 20), 48)], ids=["rows of 21 blocks", "head state 48"])
+def test_fp16_fallback_rounds_scores_like_the_fused_kernel(env, shape, hs):
+    """Configurations the fused kernel does not serve (a query row of more than 20 blocks; a head state other than 32 / 64 / 128): the operator
+    runs bst_nt and bst_masked_softmax one after the other, with the raw scores in the score type of the activations -- fp16 next to fp16 -- as
+    the fused kernel keeps them.  Against the float64 chain nt -> round to fp16 -> softmax; the same chain with bf16-rounded scores is 6e-3
+    from it (asserted on the host: at least three bars, so that this test can tell the two roundings apart)."""
+    torch, BST = env
+    heads = 2
+    lay = np.ones(shape, dtype=np.int32)
+    bst = BST(lay, block_size=32, heads=heads)
+    L = O.build_luts(lay)
+    Q, K, _, _ = _fp16_case(lay, heads, hs, 1, 77, "f16")
+    scale = 1.0 / np.sqrt(hs)
+    S = O.nt(L, Q, K, 32, heads)
+    Y16 = R.round_to(O.masked_softmax(L, R.round_to(S, "f16"), 32, scale, None), "f16")
+    Ybf = R.round_to(O.masked_softmax(L, R.round_to(S, "bf16"), 32, scale, None), "f16")
+    apart = _err(Ybf, Y16)
+    print("%s hs %d: bf16-rounded against fp16-rounded scores: L2 %.3e (bar %.1e)" % (shape, hs, apart, L2["f16"]))
+    assert apart >= 3 * L2["f16"], (shape, hs, apart)
+    tq, tk = _tt(torch, Q, "f16"), _tt(torch, K, "f16")
+    assert bst._nt_softmax(tq, tk, scale, None, torch.float16) is None, "the fused kernel serves this configuration: nothing tested"
+    y = bst.query_key_softmax(tq, tk, scale=scale)
+    assert y.dtype == torch.float16
+    err = _err(_np(y), Y16)
+    print("%s hs %d: query_key_softmax against the fp16 chain: L2 %.3e" % (shape, hs, err))
+    assert err < L2["f16"], (shape, hs, err)
+
+
+@pytest.mark.parametrize("act", ["f16", "bf16"])
+@pytest.mark.parametrize("name", ["dense rows of 20", "local strided causal"])
+def test_fused_and_composed_paths_agree_fp16(env, name, act):
+    """query_key_softmax and attention on a configuration the fused kernels serve, once as they are and once with the fused entry points of the
+    instance answering "not served" (None): the composition must give the same probabilities (no element more than one step of the score type
+    away, tensor L2 < 2e-4: the bar between the fused kernel and the two launches) and the same output and gradients (the bars of
+    test_fused_operator_gradients_match_the_composed_operators).  bf16 activations: the same pair as a regression."""
+    import _parity as P
+    torch, BST = env
+    heads, hs = 2, 64
+    if name == "dense rows of 20":
+        lay, cb, batch, seed = np.ones((1, 3, 20), dtype=np.int32), None, 1, 77
+    else:
+        lay, cb, batch, seed = O.local_strided_layout(16, local=3, stride=4), O.causal_mask_callback, 2, 43
+    Q, K, V, E = _fp16_case(lay, heads, hs, batch, seed, act)
+    scale = 1.0 / np.sqrt(hs)
+    outs = []
+    for fused in (True, False):
+        bst = BST(lay, block_size=32, heads=heads, mask_callback=cb)
+        q, k, v = (_tt(torch, a, act).requires_grad_(True) for a in (Q, K, V))
+        e = _tt(torch, E, act)
+        if fused:
+            mask_t = bst._table("mask", "cuda") if cb is not None else None
+            a0 = bst._nt_softmax(q.detach(), k.detach(), scale, mask_t, bst._score_dtype(q.dtype))
+            assert a0 is not None and bst._nt_softmax_grad(e, v.detach(), a0, scale) is not None, "the fused kernels do not serve this: nothing tested"
+        else:
+            bst._nt_softmax = lambda *args, **kw: None
+            bst._nt_softmax_grad = lambda *args, **kw: None
+        a = bst.query_key_softmax(q.detach(), k.detach(), scale=scale)
+        y = bst.attention(q, k, v, scale=scale)
+        y.backward(e)
+        outs.append((_np(a), _np(y), _np(q.grad), _np(k.grad), _np(v.grad)))
+    (a_f, *rest_f), (a_c, *rest_c) = outs
+    rep = P.block_report(a_f.reshape(-1, 1024), a_c.reshape(-1, 1024), act, a_f.size // 1024)
+    print(name, act, "probabilities, fused against composed:", rep)
+    assert rep["elem_bad"] == 0 and rep["tensor_l2"] < 2e-4, (name, act, rep)
+    for what, f, c, bar in zip(("y", "dq", "dk", "dv"), rest_f, rest_c, (1e-3, 1e-2, 1e-2, 1e-3)):
+        print(name, act, what, "fused against composed: L2 %.3e" % _err(f, c))
+        assert _err(f, c) < bar, (name, act, what, _err(f, c))

@@ -59,6 +59,48 @@ def test_prune_drops_gated_off_blocks():
     assert np.allclose(b2.fprop_test(x, W2), b.fprop_test(x, W, gate=g), atol=1e-5)
 
 
+def test_gate_kind_verdict_is_not_taken_under_capture(monkeypatch):
+    """The binary / general verdict on a gate (BlocksparseMatMul._gate_kind_of) is host state about a tensor's CONTENTS: cached per (tensor
+    object, version) for eager calls; under stream capture -- asked before the cache -- every gate is "general" and nothing is stored, because a
+    replay reads whatever the gate buffer holds by then; ``gate_kind = "binary"`` stays the caller's promise; invalidate_weights() forgets the
+    verdict, also on the quadrant operator of bsize 64 and on the doubled-table operator of gated calls.  Needs no device."""
+    import torch
+    from blocksparse_amd import BlocksparseMatMul
+    lay = P.ba_layout(12, 2, seed=4)
+    b = BlocksparseMatMul(lay, block_size=32, feature_axis=1)
+    g = torch.from_numpy((np.random.RandomState(1).rand(b.blocks) < 0.7).astype(np.float32))
+    assert b._gate_kind_of(g) == "binary"
+    hit = b._gate_kind_hit
+    assert hit is not None and hit[0]() is g and hit[2] == "binary"
+    general = torch.from_numpy(np.random.RandomState(2).uniform(0.1, 1.9, b.blocks).astype(np.float32))
+    with monkeypatch.context() as m:
+        m.setattr(torch.cuda, "is_current_stream_capturing", lambda: True)
+        assert b._gate_kind_of(g) == "general"                       # the cached verdict is not used ...
+        assert b._gate_kind_of(general) == "general"
+        assert b._gate_kind_hit is hit                               # ... and nothing is stored
+        b2 = BlocksparseMatMul(lay, block_size=32, feature_axis=1)
+        assert b2._gate_kind_of(g) == "general" and b2._gate_kind_hit is None
+        b2.gate_kind = "binary"
+        assert b2._gate_kind_of(general) == "binary"                 # the caller's promise holds under capture too
+    assert b._gate_kind_of(g) == "binary" and b._gate_kind_hit is hit
+    assert b._gate_kind_of(general) == "general" and b._gate_kind_hit[0]() is general
+    g.copy_(general)                                                 # a mutation the version counter sees
+    assert b._gate_kind_of(g) == "general"
+    g.data.copy_(torch.ones(b.blocks))                               # one it cannot see: stale until ...
+    assert b._gate_kind_of(g) == "general"
+    b.invalidate_weights()
+    assert b._gate_kind_hit is None and b._gate_kind_of(g) == "binary"
+    stale = (lambda: None, None, "binary")
+    d = b._doubled()
+    b._gate_kind_hit = d._gate_kind_hit = stale
+    b.invalidate_weights()
+    assert b._gate_kind_hit is None and d._gate_kind_hit is None
+    b64 = BlocksparseMatMul(lay, block_size=64, feature_axis=1)
+    b64._gate_kind_hit = b64._inner._gate_kind_hit = stale
+    b64.invalidate_weights()
+    assert b64._gate_kind_hit is None and b64._inner._gate_kind_hit is None
+
+
 # ---------------------------------------------------------------------------------------------------------- GPU
 @pytest.fixture(scope="module")
 def env():
