@@ -46,6 +46,7 @@ DIST_SYMBOLS = ("bsmm_dist_unique_id", "bsmm_dist_create", "bsmm_dist_allreduce_
 SPARSITY_SYMBOLS = ("bsmm_block_norm", "bsmm_block_l2_decay", "bsmm_block_threshold_prune", "bsmm_block_prune", "bsmm_feature_reduce",
                     "bsmm_reduced_dw", "bsmm_reduced_dw_workspace_bytes")      # include/bsmm_sparsity.h
 NORM_MAX, NORM_L2 = 0, 1
+OPTIM_SYMBOLS = ("bsmm_adam", "bsmm_ema", "bsmm_sum_squared", "bsmm_sum_squared_workspace_bytes", "bsmm_clip_norm")      # include/bsmm_optim.h
 BST_SYMBOLS = ("bst_nt", "bst_nn", "bst_tn", "bst_masked_softmax", "bst_softmax_grad", "bst_partial_autoregressive_mask", "bst_nt_softmax", "bst_nt_softmax_grad")
 
 
@@ -71,6 +72,19 @@ class BstArgs(ctypes.Structure):
         ("blocks", ctypes.c_int32), ("bsize", ctypes.c_int32), ("batch", ctypes.c_int32), ("heads", ctypes.c_int32),
         ("head_state", ctypes.c_int32), ("ctx_blks_q", ctypes.c_int32), ("ctx_blks_k", ctypes.c_int32),
         ("dtype", ctypes.c_int32), ("score_dtype", ctypes.c_int32), ("flags", ctypes.c_int32), ("stream", ctypes.c_void_p),
+    ]
+
+
+class BsmmAdamArgs(ctypes.Structure):
+    """Mirror of ``struct bsmm_adam_args`` (include/bsmm_optim.h)."""
+    _fields_ = [
+        ("param", ctypes.c_void_p), ("mean", ctypes.c_void_p), ("var", ctypes.c_void_p), ("grad", ctypes.c_void_p),
+        ("param16", ctypes.c_void_p), ("gate", ctypes.c_void_p), ("lr_select", ctypes.c_void_p), ("norm_scale", ctypes.c_void_p),
+        ("stream", ctypes.c_void_p), ("size", ctypes.c_size_t),
+        ("bsize", ctypes.c_int32), ("grad_dtype", ctypes.c_int32), ("param16_dtype", ctypes.c_int32),
+        ("zero_infs", ctypes.c_int32), ("zero_nans", ctypes.c_int32),
+        ("lr", ctypes.c_float), ("lr_new", ctypes.c_float), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float),
+        ("epsilon", ctypes.c_float), ("grad_scale", ctypes.c_float), ("clip_sigma", ctypes.c_float), ("saturate", ctypes.c_float),
     ]
 
 
@@ -215,6 +229,15 @@ def load():
         getattr(lib, name).restype = ctypes.c_int
     lib.bsmm_reduced_dw_workspace_bytes.argtypes = [i32, i32, i32]
     lib.bsmm_reduced_dw_workspace_bytes.restype = ctypes.c_size_t
+    # include/bsmm_optim.h
+    lib.bsmm_adam.argtypes = [ctypes.POINTER(BsmmAdamArgs)]
+    lib.bsmm_ema.argtypes = [vp, vp, vp, f32, ctypes.c_size_t, i32, i32, vp]
+    lib.bsmm_sum_squared.argtypes = [vp, ctypes.c_size_t, i32, f32, f32, i32, i32, i32, i32, vp, ctypes.c_size_t, vp]
+    lib.bsmm_clip_norm.argtypes = [vp, ctypes.c_size_t, i32, f32, vp, vp, vp]
+    for name in OPTIM_SYMBOLS:
+        getattr(lib, name).restype = ctypes.c_int
+    lib.bsmm_sum_squared_workspace_bytes.argtypes = [i32]
+    lib.bsmm_sum_squared_workspace_bytes.restype = ctypes.c_size_t
     if lib.bsmm_version() != ABI_VERSION:
         raise RuntimeError("blocksparse_amd: %s reports ABI version %d, this binding expects %d -- rebuild the library "
                            "(python -c 'import __graft_entry__ as g; g.build()')" % (LIB_PATH, lib.bsmm_version(), ABI_VERSION))
@@ -237,6 +260,16 @@ def error_string(code):
 def check(code, where):
     if code != 0:
         raise BsmmError(code, where)
+
+
+def wrote(*tensors):
+    """Tell PyTorch that a kernel of this library has written ``tensors`` in place: a store through the C ABI does not move
+    ``Tensor._version``, which autograd's saved-tensor checks and the per-weights caches of BlocksparseMatMul (prepared fp32 pieces, the
+    bsize-64 quadrant view, the gate verdict) are keyed on.  ``None`` entries are skipped."""
+    import torch
+    for t in tensors:
+        if t is not None:
+            torch.autograd.graph.increment_version(t)
 
 
 def raw_stream(device):

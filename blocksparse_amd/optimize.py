@@ -1,0 +1,277 @@
+"""Weight updates that know about gates: Adam, a moving average and the global-norm clip.
+
+The reference's names and arguments (blocksparse/optimize.py:20-110, 193-289) over the C ABI of include/bsmm_optim.h:
+
+    norm, scale = clip_by_global_norm(grads, clip_norm=1.0)        # two device fp32 scalars, no host sync; scale == 0 after an overflow
+    adam_step(w, dw, mean, var, lr, gate=gate, norm_scale=scale, param16=w16)
+    ema_step(avg, w, 0.999, gate=gate)
+
+    opt = AdamOptimizer([w, bias], learning_rate=3e-4, gated=True, working_dtype=torch.bfloat16)     # reads ``w.gate``
+    opt.step(norm_scale=scale)                                     # p.grad by default; opt.working_copy(w) is what the kernels read
+    ema = Ema(0.999, gated=True);  ema.apply([w, bias]);  ema.average(w)
+
+A block-sparse tensor is ``[blocks, bsize, bsize]`` with bsize 8 / 16 / 32 / 64; anything else (biases, embeddings) is a flat tensor and
+takes neither a gate nor an lr select.  Blocks whose gate is exactly 0 are neither read nor written -- moments, weights, the 16-bit
+working copy and the average all keep their bits.  ``lr_select`` (fp32 per block) steps the blocks with a non-zero entry at ``lr_new``:
+the blocks ``relayout`` has just added.  A ``norm_scale`` of 0 skips the whole step on the device.
+
+The learning rate is a host scalar: a step captured in a graph replays with the rate (and the step-size correction) it was captured
+with.  Every tensor a call writes gets its version counter bumped (``_lib.wrote``).  PyTorch is plumbing here as everywhere in the
+package; there is no CPU fallback.
+"""
+import ctypes
+import math
+
+from . import _lib
+
+try:
+    import torch
+except Exception:  # pragma: no cover
+    torch = None
+
+_BSIZES = (8, 16, 32, 64)
+
+
+def _dtype_code(dt):
+    from .matmul import _dtype_code as code
+    return code(dt)
+
+
+def _on_device(t, what):
+    if torch is None:
+        raise RuntimeError("blocksparse_amd needs PyTorch-ROCm for device memory")
+    if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+        raise RuntimeError("blocksparse_amd: %s must be a tensor on a ROCm device (no CPU fallback)" % what)
+    if not t.is_contiguous():
+        raise ValueError("%s must be contiguous" % what)
+
+
+def _bsize_of(param):
+    """Block size of a [blocks, bsize, bsize] tensor; 0 = a flat tensor."""
+    if param.dim() == 3 and param.shape[1] == param.shape[2] and param.shape[1] in _BSIZES:
+        return int(param.shape[1])
+    return 0
+
+
+def _like(t, ref, what, dtypes=None):
+    _on_device(t, what)
+    if t.numel() != ref.numel() or t.device != ref.device:
+        raise ValueError("%s must have the param's %d elements and device" % (what, ref.numel()))
+    if dtypes is not None and t.dtype not in dtypes:
+        raise TypeError("%s: unsupported dtype %s" % (what, t.dtype))
+
+
+def _per_block(t, param, bsize, what):
+    if t is None:
+        return None
+    if bsize == 0:
+        raise ValueError("%s needs a [blocks, bsize, bsize] param with bsize in %s, got %s" % (what, _BSIZES, tuple(param.shape)))
+    _on_device(t, what)
+    if t.dtype != torch.float32 or t.numel() != param.shape[0] or t.device != param.device:
+        raise ValueError("%s: expected a contiguous float32 tensor with one entry per block (%d) on the param's device" % (what, param.shape[0]))
+    return t.data_ptr()
+
+
+def _scalar(t, ref, what):
+    if t is None:
+        return None
+    _on_device(t, what)
+    if t.dtype != torch.float32 or t.numel() != 1 or t.device != ref.device:
+        raise ValueError("%s: expected one float32 on the param's device" % what)
+    return t.data_ptr()
+
+
+def adam_step(param, grad, mean, var, lr, beta1=0.9, beta2=0.999, epsilon=1e-8, grad_scale=1.0, clip_sigma=0.0, saturate=0.0,
+              zero_infs=False, zero_nans=False, gate=None, lr_select=None, lr_new=None, norm_scale=None, param16=None):
+    """One Adam step in place on ``param`` / ``mean`` / ``var`` (fp32) from ``grad`` (fp32 / fp16 / bf16); returns ``param``.
+    ``param16`` (fp16 / bf16) is written in the same pass: ``param`` rounded once.  See include/bsmm_optim.h for the arithmetic."""
+    _on_device(param, "param")
+    if param.dtype != torch.float32:
+        raise TypeError("param must be float32 (the 16-bit copy the kernels read is param16)")
+    bsize = _bsize_of(param)
+    _like(grad, param, "grad")
+    _like(mean, param, "mean", (torch.float32,))
+    _like(var, param, "var", (torch.float32,))
+    if param16 is not None:
+        _like(param16, param, "param16", (torch.float16, torch.bfloat16))
+    if lr_select is not None and lr_new is None:
+        raise ValueError("lr_select needs lr_new")
+    a = _lib.BsmmAdamArgs()
+    a.param, a.mean, a.var, a.grad = param.data_ptr(), mean.data_ptr(), var.data_ptr(), grad.data_ptr()
+    a.param16 = param16.data_ptr() if param16 is not None else None
+    a.gate = _per_block(gate, param, bsize, "gate")
+    a.lr_select = _per_block(lr_select, param, bsize, "lr_select")
+    a.norm_scale = _scalar(norm_scale, param, "norm_scale")
+    a.stream = _lib.raw_stream(param.device)
+    a.size, a.bsize = param.numel(), bsize
+    a.grad_dtype = _dtype_code(grad.dtype)
+    a.param16_dtype = _dtype_code(param16.dtype) if param16 is not None else 0
+    a.zero_infs, a.zero_nans = int(bool(zero_infs)), int(bool(zero_nans))
+    a.lr, a.lr_new = float(lr), float(lr_new if lr_new is not None else lr)
+    a.beta1, a.beta2, a.epsilon = float(beta1), float(beta2), float(epsilon)
+    a.grad_scale, a.clip_sigma, a.saturate = float(grad_scale), float(clip_sigma), float(saturate)
+    _lib.check(_lib.load().bsmm_adam(ctypes.byref(a)), "bsmm_adam")
+    _lib.wrote(param, mean, var, param16)
+    return param
+
+
+def ema_step(ema, param, decay, gate=None):
+    """``ema -= (1 - decay) * (ema - param)`` in place (``ema``: fp32 / fp16 / bf16, ``param``: fp32); returns ``ema``."""
+    _on_device(param, "param")
+    if param.dtype != torch.float32:
+        raise TypeError("param must be float32")
+    bsize = _bsize_of(param)
+    _like(ema, param, "ema")
+    _lib.check(_lib.load().bsmm_ema(ema.data_ptr(), param.data_ptr(), _per_block(gate, param, bsize, "gate"), float(decay), param.numel(), bsize,
+                                    _dtype_code(ema.dtype), _lib.raw_stream(param.device)), "bsmm_ema")
+    _lib.wrote(ema)
+    return ema
+
+
+def clip_by_global_norm(grads, clip_norm=1.0, grad_scale=1.0, saturate=0.0, zero_infs=False, zero_nans=False):
+    """``(global_norm, norm_scale)`` of a list of gradients (mixed dtypes allowed): two device fp32 scalars, no host sync.
+    ``global_norm = sqrt(sum (grad_scale * g)^2)``; ``norm_scale = clip_norm / max(global_norm, clip_norm)``, or 0 when the norm is not
+    finite -- the value that makes ``adam_step`` skip.  Deterministic: the same gradients at the same addresses give the same bits."""
+    grads = list(grads)
+    if not grads:
+        raise ValueError("clip_by_global_norm needs at least one gradient")
+    for g in grads:
+        _on_device(g, "grad")
+        if g.device != grads[0].device:
+            raise ValueError("all gradients must be on one device")
+        if g.numel() == 0:
+            raise ValueError("empty gradient")
+    lib = _lib.load()
+    dev = grads[0].device
+    cnt = len(grads)
+    need = int(lib.bsmm_sum_squared_workspace_bytes(cnt))
+    ws = torch.empty(need // 4, dtype=torch.float32, device=dev)
+    out = torch.empty(2, dtype=torch.float32, device=dev)
+    st = _lib.raw_stream(dev)
+    for i, g in enumerate(grads):
+        _lib.check(lib.bsmm_sum_squared(g.data_ptr(), g.numel(), _dtype_code(g.dtype), float(grad_scale), float(saturate), int(bool(zero_infs)),
+                                        int(bool(zero_nans)), i, cnt, ws.data_ptr(), need, st), "bsmm_sum_squared")
+    _lib.check(lib.bsmm_clip_norm(ws.data_ptr(), need, cnt, float(clip_norm), out.data_ptr(), out.data_ptr() + 4, st), "bsmm_clip_norm")
+    return out[0], out[1]
+
+
+def global_norm(grads, grad_scale=1.0, saturate=0.0, zero_infs=False, zero_nans=False):
+    """The global norm alone (blocksparse/optimize.py:222-224)."""
+    return clip_by_global_norm(grads, clip_norm=9e9, grad_scale=grad_scale, saturate=saturate, zero_infs=zero_infs, zero_nans=zero_nans)[0]
+
+
+def lr_correction(step, beta1, beta2, zero_init_variables=False):
+    """``sqrt(1 - beta2^t) / (1 - beta1^t)`` for call number ``step`` (1, 2, ...): the reference's beta-power accumulators start at beta and
+    are multiplied by beta after every call (blocksparse/optimize.py:45-57, 104-110).  With ``zero_init_variables`` they start at 0 and
+    stay there: no correction, the setting for moments that are loaded rather than grown from zero."""
+    if zero_init_variables:
+        return 1.0
+    t = max(int(step), 1)
+    return math.sqrt(1.0 - beta2 ** t) / (1.0 - beta1 ** t)
+
+
+class AdamOptimizer(object):
+    """Adam over a list of fp32 tensors (block-sparse or flat) with fp32 ``Mean`` / ``Var`` slots.  ``gated=True`` reads ``param.gate``.
+    ``working_dtype``: keep a 16-bit copy of every param, rewritten by the step itself (``working_copy(param)``)."""
+
+    def __init__(self, params, learning_rate=3e-4, beta1=0.9, beta2=0.999, epsilon=1e-8, clip_sigmas=0.0, norm_scale=None, grad_scale=1.0,
+                 saturate=0.0, zero_infs=False, zero_nans=False, gated=False, zero_init_variables=False, working_dtype=None):
+        self.params = list(params)
+        if not self.params:
+            raise ValueError("AdamOptimizer needs at least one param")
+        self.learning_rate, self.beta1, self.beta2, self.epsilon = float(learning_rate), float(beta1), float(beta2), float(epsilon)
+        self.clip_sigmas, self.grad_scale, self.saturate = float(clip_sigmas), float(grad_scale), float(saturate)
+        self.zero_infs, self.zero_nans, self.gated, self.zero_init_variables = bool(zero_infs), bool(zero_nans), bool(gated), bool(zero_init_variables)
+        self.norm_scale = norm_scale
+        self.working_dtype = working_dtype
+        self.steps = 0
+        self.slots = []
+        for p in self.params:
+            _on_device(p, "param")
+            if p.dtype != torch.float32:
+                raise TypeError("AdamOptimizer keeps fp32 params (working_dtype gives the 16-bit copies)")
+            d = p.detach()
+            slot = {"Mean": torch.zeros_like(d), "Var": torch.zeros_like(d)}
+            if working_dtype is not None:
+                slot["working"] = d.to(working_dtype)
+            self.slots.append(slot)
+
+    def _index(self, param):
+        for i, p in enumerate(self.params):
+            if p is param:
+                return i
+        raise KeyError("not a param of this optimizer")
+
+    def get_slot(self, param, name):
+        """The ``"Mean"`` or ``"Var"`` tensor of ``param``."""
+        return self.slots[self._index(param)][name]
+
+    def working_copy(self, param):
+        """The 16-bit copy of ``param`` (``None`` without ``working_dtype``)."""
+        return self.slots[self._index(param)].get("working")
+
+    def current_lr(self, learning_rate=None):
+        """The corrected step size of the most recent call of ``step``."""
+        lr = self.learning_rate if learning_rate is None else float(learning_rate)
+        return lr * lr_correction(self.steps, self.beta1, self.beta2, self.zero_init_variables)
+
+    def step(self, grads=None, lr_select=None, lr_new=None, norm_scale=None):
+        """One step for every param.  ``grads``: a list parallel to the params (default: ``p.grad``; params without one are left out).
+        ``lr_select``: a list parallel to the params (``None`` entries allowed) or a dict ``{param index: tensor}``; ``lr_new``: the rate
+        of the selected blocks, corrected like the learning rate.  ``norm_scale`` overrides the constructor's.  The step counter advances on
+        every call, also when the device skips the step."""
+        self.steps += 1
+        lr = self.current_lr()
+        lr_new_t = self.current_lr(lr_new) if lr_new is not None else None
+        ns = norm_scale if norm_scale is not None else self.norm_scale
+        if grads is None:
+            grads = [p.grad for p in self.params]
+        grads = list(grads)
+        if len(grads) != len(self.params):
+            raise ValueError("need one gradient (or None) per param")
+        for i, (p, g) in enumerate(zip(self.params, grads)):
+            if g is None:
+                continue
+            sel = lr_select.get(i) if isinstance(lr_select, dict) else (lr_select[i] if lr_select is not None else None)
+            gate = getattr(p, "gate", None) if self.gated else None
+            slot = self.slots[i]
+            adam_step(p.detach(), g.detach(), slot["Mean"], slot["Var"], lr, beta1=self.beta1, beta2=self.beta2, epsilon=self.epsilon,
+                      grad_scale=self.grad_scale, clip_sigma=self.clip_sigmas, saturate=self.saturate, zero_infs=self.zero_infs,
+                      zero_nans=self.zero_nans, gate=gate, lr_select=sel, lr_new=lr_new_t if sel is not None else None, norm_scale=ns,
+                      param16=slot.get("working"))
+
+    def state_dict(self):
+        return {"steps": self.steps, "slots": [{"Mean": s["Mean"].clone(), "Var": s["Var"].clone()} for s in self.slots]}
+
+    def load_state_dict(self, state):
+        if len(state["slots"]) != len(self.slots):
+            raise ValueError("state has %d slots, the optimizer %d params" % (len(state["slots"]), len(self.slots)))
+        for s, new in zip(self.slots, state["slots"]):
+            s["Mean"].copy_(new["Mean"])
+            s["Var"].copy_(new["Var"])
+        self.steps = int(state["steps"])
+        for p, s in zip(self.params, self.slots):          # the working copies follow the params the caller has loaded
+            if "working" in s:
+                s["working"].copy_(p.detach())
+
+
+class Ema(object):
+    """Moving averages of a set of params (blocksparse/optimize.py:235-289).  ``apply(params)`` updates them (an average starts as a copy
+    of its param), ``average(param)`` returns one.  ``gated=True`` reads ``param.gate``; ``dtype``: storage type of the averages (fp32)."""
+
+    def __init__(self, decay=0.999, gated=False, dtype=None):
+        self.decay, self.gated, self.dtype = float(decay), bool(gated), dtype
+        self.averages = {}                                  # id(param) -> (param, average): the param is held so that its id stays its own
+
+    def apply(self, params):
+        for p in params:
+            _on_device(p, "param")
+            ent = self.averages.get(id(p))
+            if ent is None:
+                ent = self.averages[id(p)] = (p, p.detach().to(self.dtype or torch.float32, copy=True))
+            gate = getattr(p, "gate", None) if self.gated else None
+            ema_step(ent[1], p.detach(), self.decay, gate=gate)
+
+    def average(self, param):
+        ent = self.averages.get(id(param))
+        return ent[1] if ent is not None else None

@@ -73,6 +73,7 @@ def blocksparse_l2_decay(param, gate=None, rate=0.05, epsilon=1e-12):
     _lib.check(_lib.load().bsmm_block_l2_decay(param.data_ptr(), gate.data_ptr() if gate is not None else None, float(rate), float(epsilon),
                                                param.shape[0], param.shape[1], _dtype_code(param.dtype), _lib.raw_stream(param.device)),
                "bsmm_block_l2_decay")
+    _lib.wrote(param)
     return param
 
 
@@ -105,6 +106,7 @@ def blocksparse_prune(param, gate, step, sparsity=None, threshold=None, norm="ma
     else:
         _lib.check(lib.bsmm_block_threshold_prune(param.data_ptr(), gate.data_ptr(), float(threshold), code, blocks, param.shape[1],
                                                   _dtype_code(param.dtype), st), "bsmm_block_threshold_prune")
+    _lib.wrote(gate)
     return gate
 
 
