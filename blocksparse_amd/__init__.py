@@ -8,6 +8,6 @@ from . import checkpoint  # noqa: F401
 from . import sparsity  # noqa: F401
 from .sparsity import blocksparse_norm, blocksparse_l2_decay, blocksparse_prune  # noqa: F401
 from . import optimize  # noqa: F401
-from .optimize import AdamOptimizer, Ema, adam_step, ema_step, clip_by_global_norm, global_norm  # noqa: F401
+from .optimize import AdamOptimizer, Ema, PreparedStep, adam_step, ema_step, clip_by_global_norm, global_norm  # noqa: F401
 
 __version__ = "0.1.0"

@@ -47,6 +47,8 @@ SPARSITY_SYMBOLS = ("bsmm_block_norm", "bsmm_block_l2_decay", "bsmm_block_thresh
                     "bsmm_reduced_dw", "bsmm_reduced_dw_workspace_bytes")      # include/bsmm_sparsity.h
 NORM_MAX, NORM_L2 = 0, 1
 OPTIM_SYMBOLS = ("bsmm_adam", "bsmm_ema", "bsmm_sum_squared", "bsmm_sum_squared_workspace_bytes", "bsmm_clip_norm")      # include/bsmm_optim.h
+OPTIM_LIST_SYMBOLS = ("bsmm_opt_list_bytes", "bsmm_opt_list_build", "bsmm_opt_advance", "bsmm_adam_list", "bsmm_ema_list",
+                      "bsmm_sum_squared_list")      # include/bsmm_optim_list.h
 BST_SYMBOLS = ("bst_nt", "bst_nn", "bst_tn", "bst_masked_softmax", "bst_softmax_grad", "bst_partial_autoregressive_mask", "bst_nt_softmax", "bst_nt_softmax_grad")
 
 
@@ -85,6 +87,37 @@ class BsmmAdamArgs(ctypes.Structure):
         ("zero_infs", ctypes.c_int32), ("zero_nans", ctypes.c_int32),
         ("lr", ctypes.c_float), ("lr_new", ctypes.c_float), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float),
         ("epsilon", ctypes.c_float), ("grad_scale", ctypes.c_float), ("clip_sigma", ctypes.c_float), ("saturate", ctypes.c_float),
+    ]
+
+
+class BsmmOptTensor(ctypes.Structure):
+    """Mirror of ``struct bsmm_opt_tensor`` (include/bsmm_optim_list.h): one row of a tensor list."""
+    _fields_ = [
+        ("param", ctypes.c_void_p), ("mean", ctypes.c_void_p), ("var", ctypes.c_void_p), ("grad", ctypes.c_void_p),
+        ("param16", ctypes.c_void_p), ("gate", ctypes.c_void_p), ("lr_select", ctypes.c_void_p), ("ema", ctypes.c_void_p),
+        ("size", ctypes.c_size_t),
+        ("bsize", ctypes.c_int32), ("grad_dtype", ctypes.c_int32), ("param16_dtype", ctypes.c_int32), ("ema_dtype", ctypes.c_int32),
+    ]
+
+
+class BsmmOptList(ctypes.Structure):
+    """Mirror of ``struct bsmm_opt_list`` (include/bsmm_optim_list.h): what the host keeps of a built table."""
+    _fields_ = [
+        ("table_bytes", ctypes.c_size_t),
+        ("count", ctypes.c_int32), ("adam_grid", ctypes.c_int32), ("ema_grid", ctypes.c_int32), ("sum_squared_grid", ctypes.c_int32),
+    ]
+
+
+class BsmmOptState(ctypes.Structure):
+    """Mirror of ``struct bsmm_opt_state`` (include/bsmm_optim_list.h): the 16 bytes of step state that live on the device."""
+    _fields_ = [("step", ctypes.c_int32), ("lr_t", ctypes.c_float), ("lr_new_t", ctypes.c_float), ("reserved", ctypes.c_int32)]
+
+
+class BsmmAdamSettings(ctypes.Structure):
+    """Mirror of ``struct bsmm_adam_settings`` (include/bsmm_optim_list.h)."""
+    _fields_ = [
+        ("beta1", ctypes.c_float), ("beta2", ctypes.c_float), ("epsilon", ctypes.c_float), ("grad_scale", ctypes.c_float),
+        ("clip_sigma", ctypes.c_float), ("saturate", ctypes.c_float), ("zero_infs", ctypes.c_int32), ("zero_nans", ctypes.c_int32),
     ]
 
 
@@ -238,6 +271,17 @@ def load():
         getattr(lib, name).restype = ctypes.c_int
     lib.bsmm_sum_squared_workspace_bytes.argtypes = [i32]
     lib.bsmm_sum_squared_workspace_bytes.restype = ctypes.c_size_t
+    # include/bsmm_optim_list.h
+    plist = ctypes.POINTER(BsmmOptList)
+    lib.bsmm_opt_list_build.argtypes = [ctypes.POINTER(BsmmOptTensor), i32, vp, ctypes.c_size_t, plist]
+    lib.bsmm_opt_advance.argtypes = [vp, vp, vp, ctypes.c_double, ctypes.c_double, i32, vp]
+    lib.bsmm_adam_list.argtypes = [plist, vp, vp, vp, ctypes.POINTER(BsmmAdamSettings), vp]
+    lib.bsmm_ema_list.argtypes = [plist, vp, f32, vp]
+    lib.bsmm_sum_squared_list.argtypes = [plist, vp, f32, f32, i32, i32, vp, ctypes.c_size_t, vp]
+    for name in OPTIM_LIST_SYMBOLS:
+        getattr(lib, name).restype = ctypes.c_int
+    lib.bsmm_opt_list_bytes.argtypes = [i32]
+    lib.bsmm_opt_list_bytes.restype = ctypes.c_size_t
     if lib.bsmm_version() != ABI_VERSION:
         raise RuntimeError("blocksparse_amd: %s reports ABI version %d, this binding expects %d -- rebuild the library "
                            "(python -c 'import __graft_entry__ as g; g.build()')" % (LIB_PATH, lib.bsmm_version(), ABI_VERSION))

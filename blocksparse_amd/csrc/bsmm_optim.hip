@@ -140,7 +140,7 @@ int bsmm_clip_norm(const void* workspace, size_t workspace_bytes, int32_t tensor
     if (norm_out == nullptr || scale_out == nullptr || tensor_cnt <= 0) return BSMM_ERR_ARG;
     if (tensor_cnt > (1 << 20)) return BSMM_ERR_UNSUPPORTED;
     if (!workspace_ok(workspace, workspace_bytes, tensor_cnt)) return BSMM_ERR_WORKSPACE;
-    opt_clip_norm_kernel<<<1, OPT_THREADS, 0, static_cast<hipStream_t>(stream)>>>(static_cast<const float*>(workspace), tensor_cnt * OPT_SS_SLOTS, clip_norm,
+    opt_clip_norm_kernel<0><<<1, OPT_THREADS, 0, static_cast<hipStream_t>(stream)>>>(static_cast<const float*>(workspace), tensor_cnt * OPT_SS_SLOTS, clip_norm,
                                                                                   norm_out, scale_out);
     return (int)hipGetLastError();
 }

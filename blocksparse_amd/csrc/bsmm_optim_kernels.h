@@ -81,6 +81,7 @@ __device__ __forceinline__ int opt_block_of(size_t i, int bb, bool uniform) {
 
 // ---- Adam -------------------------------------------------------------------------------------------------------------------------
 // GT: gradient type; PT: type of the 16-bit working copy or NoP16; VEC: the vector path
+// (opt_adam_row in bsmm_optim_list_kernels.h is this loop for workgroup w of G of one row of a list: an edit here is an edit there)
 template <class GT, class PT, bool VEC>
 __global__ void __launch_bounds__(OPT_THREADS) opt_adam_kernel(float* __restrict__ param, float* __restrict__ mean, float* __restrict__ var,
                                                                const typename GT::T* __restrict__ grad, void* __restrict__ param16,
@@ -137,6 +138,8 @@ __global__ void __launch_bounds__(OPT_THREADS) opt_adam_kernel(float* __restrict
 // ---- moving average: e -= (1 - decay) (e - p) ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ float ema_elem(float e, float p, float rate) { return e - rate * (e - p); }
 
+// (opt_ema_row in bsmm_optim_list_kernels.h is this loop for one row of a list: an edit here is an edit there)
+
 template <class ET, bool VEC>
 __global__ void __launch_bounds__(OPT_THREADS) opt_ema_kernel(typename ET::T* __restrict__ ema, const float* __restrict__ param,
                                                               const float* __restrict__ gate, size_t size, int bb, float rate) {
@@ -180,6 +183,7 @@ __device__ __forceinline__ float opt_group_sum(float acc, float* share) {
 
 // VEC: a lane loads 16 bytes (4 fp32 or 8 16-bit elements) per step.  The grid is min(OPT_SS_SLOTS, ceil(steps / 256)) workgroups -- a
 // function of size and path -- and workgroup w stores slot w; the slots from gridDim.x on are stored as 0.
+// (opt_sum_squared_row in bsmm_optim_list_kernels.h is this body for one row of a list and must add in this order: an edit here is an edit there)
 template <class DT, bool VEC>
 __global__ void __launch_bounds__(OPT_THREADS) opt_sum_squared_kernel(const typename DT::T* __restrict__ x, float* __restrict__ slots, size_t size,
                                                                       float grad_scale, float saturate, int zero_infs, int zero_nans) {
@@ -218,7 +222,8 @@ __global__ void __launch_bounds__(OPT_THREADS) opt_sum_squared_kernel(const type
     for (size_t s = (size_t)gridDim.x + tid; s < (size_t)OPT_SS_SLOTS; s += nthreads) slots[s] = 0.f;
 }
 
-// ---- global norm, stage 2: one workgroup -------------------------------------------------------------------------------------------------
+// ---- global norm, stage 2: one workgroup (a template only so that two translation units may include this header) --------------------------
+template <int UNUSED = 0>
 __global__ void __launch_bounds__(OPT_THREADS) opt_clip_norm_kernel(const float* __restrict__ slots, int count, float clip_norm,
                                                                     float* __restrict__ norm_out, float* __restrict__ scale_out) {
     __shared__ float share[4];

@@ -15,9 +15,16 @@ takes neither a gate nor an lr select.  Blocks whose gate is exactly 0 are neith
 working copy and the average all keep their bits.  ``lr_select`` (fp32 per block) steps the blocks with a non-zero entry at ``lr_new``:
 the blocks ``relayout`` has just added.  A ``norm_scale`` of 0 skips the whole step on the device.
 
-The learning rate is a host scalar: a step captured in a graph replays with the rate (and the step-size correction) it was captured
-with.  Every tensor a call writes gets its version counter bumped (``_lib.wrote``).  PyTorch is plumbing here as everywhere in the
-package; there is no CPU fallback.
+For these per-tensor calls the learning rate is a host scalar: a step captured in a graph replays with the rate (and the step-size
+correction) it was captured with.  The list form (include/bsmm_optim_list.h) lifts both limits:
+
+    step = opt.prepare(clip_norm=1.0, ema=ema)                     # binds p, p.grad, slots, gates, averages: one table on the device
+    step.learning_rate.fill_(schedule(t))                          # a device fp32 [1]: ordinary device work, inside or outside a graph
+    step.run()                                                     # at most 5 launches whatever len(params); capturable
+
+with the step number and the corrected rates on the device, so a captured step follows a schedule.  Its results equal the per-tensor
+calls bit for bit.  Every tensor a call writes gets its version counter bumped (``_lib.wrote``).  PyTorch is plumbing here as everywhere
+in the package; there is no CPU fallback.
 """
 import ctypes
 import math
@@ -240,6 +247,14 @@ class AdamOptimizer(object):
                       zero_nans=self.zero_nans, gate=gate, lr_select=sel, lr_new=lr_new_t if sel is not None else None, norm_scale=ns,
                       param16=slot.get("working"))
 
+    def prepare(self, grads=None, clip_norm=None, ema=None, lr_select=None, lr_new=None, ema_params=None):
+        """Bind every tensor of the update once and return a ``PreparedStep`` whose ``run()`` is [sum of squares, clip,] advance, Adam
+        [, moving average]: one launch per stage over all params.  ``grads``: a list parallel to the params (default ``p.grad``; every
+        param must have one).  ``clip_norm``: clip by the global norm of the grads first (else the constructor's ``norm_scale``, if any,
+        scales them).  ``ema``: an ``Ema`` whose averages follow the step (created as ``Ema.apply`` creates them; ``ema_params``
+        restricts them to some of the params).  ``lr_select``: a list or dict as in ``step`` (``None`` entries allowed), with ``lr_new``."""
+        return PreparedStep(self, grads, clip_norm, ema, lr_select, lr_new, ema_params)
+
     def state_dict(self):
         return {"steps": self.steps, "slots": [{"Mean": s["Mean"].clone(), "Var": s["Var"].clone()} for s in self.slots]}
 
@@ -253,6 +268,167 @@ class AdamOptimizer(object):
         for p, s in zip(self.params, self.slots):          # the working copies follow the params the caller has loaded
             if "working" in s:
                 s["working"].copy_(p.detach())
+
+
+class PreparedStep(object):
+    """The list form of one optimizer step (``AdamOptimizer.prepare``): the tensors are bound once, in a table on the device, and every
+    stage walks the table in one launch.  The step number and the corrected rates live on the device:
+
+        learning_rate   device fp32 [1], starts at ``opt.learning_rate``; write it with ``fill_`` / ``copy_`` (a schedule)
+        lr_new          device fp32 [1], or None without ``lr_new``
+        global_norm, norm_scale   device scalars of the last run (None without ``clip_norm``)
+        rates()         device fp32 [2]: the corrected ``lr_t, lr_new_t`` of the last run
+        sync_host()     reads the device step count into ``opt.steps`` -- the one host sync; needed before ``state_dict()`` after replays
+
+    The table holds addresses: ``run()`` refuses to launch when a bound tensor has moved (``p.grad`` reallocated -- keep it with
+    ``zero_grad(set_to_none=False)``).  Results equal those of the per-tensor calls bit for bit."""
+
+    def __init__(self, opt, grads, clip_norm, ema, lr_select, lr_new, ema_params):
+        self.opt = opt
+        params = opt.params
+        dev = params[0].device
+        if grads is not None:
+            grads = list(grads)
+            if len(grads) != len(params):
+                raise ValueError("need one gradient per param")
+        if lr_select is not None and lr_new is None:
+            raise ValueError("lr_select needs lr_new")
+        if ema is not None and ema.gated != opt.gated:
+            raise ValueError("the list step reads one gate per param: Ema.gated and AdamOptimizer.gated must agree")
+        if ema_params is not None and ema is None:
+            raise ValueError("ema_params needs ema")
+        averaged = None if ema_params is None else set(id(p) for p in ema_params)
+        self._bound = []                                    # (what, how to find the tensor now, its address, type and size when bound)
+        self._held = []                                     # every bound tensor stays alive as long as the table does
+        self._written = []
+
+        def bind(what, get):
+            t = get()
+            self._bound.append((what, get, (t.data_ptr(), t.dtype, t.numel())))
+            self._held.append(t)
+            return t.data_ptr()
+
+        rows = (_lib.BsmmOptTensor * len(params))()
+        for i, p in enumerate(params):
+            if p.device != dev:
+                raise ValueError("all params must be on one device")
+            d = p.detach()
+            bsize = _bsize_of(d)
+            if grads is None:
+                if p.grad is None:
+                    raise ValueError("param %d has no grad: every param of a prepared step needs one" % i)
+                g = p.grad
+                get_grad = lambda p=p: p.grad
+            else:
+                g = grads[i]
+                if g is None:
+                    raise ValueError("param %d has no grad: every param of a prepared step needs one" % i)
+                g = g.detach()
+                get_grad = lambda g=g: g
+            _like(g, d, "grad")
+            slot = opt.slots[i]
+            _like(slot["Mean"], d, "mean", (torch.float32,))
+            _like(slot["Var"], d, "var", (torch.float32,))
+            r = rows[i]
+            r.param = bind("param %d" % i, lambda p=p: p)
+            r.grad = bind("the grad of param %d" % i, get_grad)
+            r.mean = bind("Mean of param %d" % i, lambda slot=slot: slot["Mean"])
+            r.var = bind("Var of param %d" % i, lambda slot=slot: slot["Var"])
+            self._written += [d, slot["Mean"], slot["Var"]]
+            self._held.append(d)
+            r.size, r.bsize, r.grad_dtype = d.numel(), bsize, _dtype_code(g.dtype)
+            work = slot.get("working")
+            if work is not None:
+                _like(work, d, "param16", (torch.float16, torch.bfloat16))
+                r.param16 = bind("the working copy of param %d" % i, lambda slot=slot: slot["working"])
+                r.param16_dtype = _dtype_code(work.dtype)
+                self._written.append(work)
+            gate = getattr(p, "gate", None) if opt.gated else None
+            if gate is not None:
+                _per_block(gate, d, bsize, "gate")
+                r.gate = bind("the gate of param %d" % i, lambda p=p: p.gate)
+            sel = lr_select.get(i) if isinstance(lr_select, dict) else (lr_select[i] if lr_select is not None else None)
+            if sel is not None:
+                _per_block(sel, d, bsize, "lr_select")
+                r.lr_select = bind("lr_select of param %d" % i, lambda sel=sel: sel)
+            if ema is not None and (averaged is None or id(p) in averaged):
+                ent = ema.averages.get(id(p))
+                if ent is None:
+                    ent = ema.averages[id(p)] = (p, d.to(ema.dtype or torch.float32, copy=True))
+                _like(ent[1], d, "ema")
+                r.ema = bind("the average of param %d" % i, lambda ema=ema, p=p: ema.averages[id(p)][1])
+                r.ema_dtype = _dtype_code(ent[1].dtype)
+                self._written.append(ent[1])
+        lib = _lib.load()
+        self._info = _lib.BsmmOptList()
+        nbytes = int(lib.bsmm_opt_list_bytes(len(params)))
+        host = (ctypes.c_ubyte * max(nbytes, 1))()
+        _lib.check(lib.bsmm_opt_list_build(rows, len(params), host, nbytes, ctypes.byref(self._info)), "bsmm_opt_list_build")
+        self._table = torch.frombuffer(host, dtype=torch.uint8, count=nbytes).to(dev)
+        assert self._table.data_ptr() % 16 == 0
+        self._state = torch.zeros(4, dtype=torch.int32, device=dev)
+        self._state[0] = opt.steps
+        self._steps = opt.steps                             # the host count the device state was last level with
+        self.learning_rate = torch.full((1,), opt.learning_rate, dtype=torch.float32, device=dev)
+        self.lr_new = torch.full((1,), float(lr_new), dtype=torch.float32, device=dev) if lr_new is not None else None
+        self.ema = ema
+        self.clip_norm = None if clip_norm is None else float(clip_norm)
+        self.global_norm = self.norm_scale = None
+        self._ns = _scalar(opt.norm_scale, params[0], "norm_scale")
+        if opt.norm_scale is not None:
+            self._held.append(opt.norm_scale)
+        if clip_norm is not None:
+            self._ws_bytes = int(lib.bsmm_sum_squared_workspace_bytes(len(params)))
+            self._ws = torch.empty(self._ws_bytes // 4, dtype=torch.float32, device=dev)
+            out = torch.zeros(2, dtype=torch.float32, device=dev)
+            self.global_norm, self.norm_scale = out[0], out[1]
+            self._ns = out.data_ptr() + 4
+        self._settings = s = _lib.BsmmAdamSettings()
+        s.beta1, s.beta2, s.epsilon, s.grad_scale, s.clip_sigma, s.saturate = opt.beta1, opt.beta2, opt.epsilon, opt.grad_scale, opt.clip_sigmas, opt.saturate
+        s.zero_infs, s.zero_nans = int(opt.zero_infs), int(opt.zero_nans)
+        self._device = dev
+
+    def rates(self):
+        """Device fp32 [2]: the corrected rates ``lr_t, lr_new_t`` the last run stepped with (a view of the device state)."""
+        return self._state[1:3].view(torch.float32)
+
+    def sync_host(self):
+        """Read the device step count into ``opt.steps`` (a host sync) and return it."""
+        self.opt.steps = self._steps = int(self._state[0].item())
+        return self.opt.steps
+
+    def _check_bound(self):
+        for what, get, was in self._bound:
+            t = get()
+            if t is None or (t.data_ptr(), t.dtype, t.numel()) != was:          # (the allocator may hand a new tensor the old address)
+                raise ValueError("%s has moved since prepare(): the table holds its old address.  Keep gradients in place with "
+                                 "zero_grad(set_to_none=False) (or copy_ into them), or prepare() again" % what)
+
+    def run(self):
+        """One step: [sum of squares, clip,] advance, Adam [, moving average].  Only enqueues; capturable.  The device owns the step count:
+        a replay advances it without the host seeing it, so after replays ``opt.steps`` is behind until ``sync_host()`` (an eager run does
+        not catch it up; it only levels the device with a count the host has SET since, as ``load_state_dict`` does)."""
+        opt, lib, info = self.opt, _lib.load(), ctypes.byref(self._info)
+        capturing = torch.cuda.is_current_stream_capturing()
+        if not capturing:
+            self._check_bound()
+            if opt.steps != self._steps:                    # the host count was set since (load_state_dict): level the device with it
+                self._state[0] = opt.steps
+        st, table, state = _lib.raw_stream(self._device), self._table.data_ptr(), self._state.data_ptr()
+        if self.clip_norm is not None:
+            _lib.check(lib.bsmm_sum_squared_list(info, table, opt.grad_scale, opt.saturate, int(opt.zero_infs), int(opt.zero_nans),
+                                                 self._ws.data_ptr(), self._ws_bytes, st), "bsmm_sum_squared_list")
+            _lib.check(lib.bsmm_clip_norm(self._ws.data_ptr(), self._ws_bytes, self._info.count, self.clip_norm, self.global_norm.data_ptr(),
+                                          self.norm_scale.data_ptr(), st), "bsmm_clip_norm")
+        _lib.check(lib.bsmm_opt_advance(state, self.learning_rate.data_ptr(), self.lr_new.data_ptr() if self.lr_new is not None else None,
+                                        opt.beta1, opt.beta2, int(opt.zero_init_variables), st), "bsmm_opt_advance")
+        _lib.check(lib.bsmm_adam_list(info, table, state, self._ns, ctypes.byref(self._settings), st), "bsmm_adam_list")
+        if self.ema is not None:
+            _lib.check(lib.bsmm_ema_list(info, table, self.ema.decay, st), "bsmm_ema_list")
+        _lib.wrote(*self._written)
+        if not capturing:
+            opt.steps += 1
+            self._steps = opt.steps
 
 
 class Ema(object):

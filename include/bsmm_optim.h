@@ -33,7 +33,8 @@ extern "C" {
  * with IEEE square root and division.  A block whose gate is exactly 0 is neither read nor written, in any tensor.  Blocks whose
  * lr_select entry is non-zero step with lr_new, the others with lr.  *norm_scale == 0 is the "skip this step" sentinel of
  * bsmm_clip_norm: nothing at all is stored.  param16, where given, is written wherever param is: param rounded once to nearest-even.
- * lr is a host scalar: a captured step replays with the lr it was captured with. */
+ * lr is a host scalar here: a captured step replays with the lr it was captured with.  bsmm_adam_list (bsmm_optim_list.h) reads the rates
+ * from a device-resident step state instead, and steps a whole list of tensors in one launch. */
 typedef struct bsmm_adam_args {
     float* param;             /* fp32 [size] */
     float* mean;              /* fp32 [size] */
