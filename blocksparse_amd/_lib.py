@@ -49,6 +49,7 @@ NORM_MAX, NORM_L2 = 0, 1
 OPTIM_SYMBOLS = ("bsmm_adam", "bsmm_ema", "bsmm_sum_squared", "bsmm_sum_squared_workspace_bytes", "bsmm_clip_norm")      # include/bsmm_optim.h
 OPTIM_LIST_SYMBOLS = ("bsmm_opt_list_bytes", "bsmm_opt_list_build", "bsmm_opt_advance", "bsmm_adam_list", "bsmm_ema_list",
                       "bsmm_sum_squared_list")      # include/bsmm_optim_list.h
+NORM_SYMBOLS = ("bsmm_layer_norm", "bsmm_layer_norm_grad", "bsmm_layer_norm_workspace_bytes")      # include/bsmm_norm.h
 BST_SYMBOLS = ("bst_nt", "bst_nn", "bst_tn", "bst_masked_softmax", "bst_softmax_grad", "bst_partial_autoregressive_mask", "bst_nt_softmax", "bst_nt_softmax_grad")
 
 
@@ -118,6 +119,15 @@ class BsmmAdamSettings(ctypes.Structure):
     _fields_ = [
         ("beta1", ctypes.c_float), ("beta2", ctypes.c_float), ("epsilon", ctypes.c_float), ("grad_scale", ctypes.c_float),
         ("clip_sigma", ctypes.c_float), ("saturate", ctypes.c_float), ("zero_infs", ctypes.c_int32), ("zero_nans", ctypes.c_int32),
+    ]
+
+
+class BsmmLnArgs(ctypes.Structure):
+    """Mirror of ``struct bsmm_ln_args`` (include/bsmm_norm.h)."""
+    _fields_ = [
+        ("K", ctypes.c_int32), ("N", ctypes.c_int32), ("segments", ctypes.c_int32), ("axis", ctypes.c_int32),
+        ("dtype", ctypes.c_int32), ("relu", ctypes.c_int32), ("epsilon", ctypes.c_float),
+        ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t), ("stream", ctypes.c_void_p),
     ]
 
 
@@ -282,6 +292,14 @@ def load():
         getattr(lib, name).restype = ctypes.c_int
     lib.bsmm_opt_list_bytes.argtypes = [i32]
     lib.bsmm_opt_list_bytes.restype = ctypes.c_size_t
+    # include/bsmm_norm.h
+    pln = ctypes.POINTER(BsmmLnArgs)
+    lib.bsmm_layer_norm.argtypes = [vp, vp, vp, vp, vp, vp, pln]
+    lib.bsmm_layer_norm.restype = ctypes.c_int
+    lib.bsmm_layer_norm_grad.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, pln]
+    lib.bsmm_layer_norm_grad.restype = ctypes.c_int
+    lib.bsmm_layer_norm_workspace_bytes.argtypes = [pln, i32]
+    lib.bsmm_layer_norm_workspace_bytes.restype = ctypes.c_size_t
     if lib.bsmm_version() != ABI_VERSION:
         raise RuntimeError("blocksparse_amd: %s reports ABI version %d, this binding expects %d -- rebuild the library "
                            "(python -c 'import __graft_entry__ as g; g.build()')" % (LIB_PATH, lib.bsmm_version(), ABI_VERSION))

@@ -1,0 +1,219 @@
+"""CPU tier of the layer norm (include/bsmm_norm.h, blocksparse_amd/norms.py): the exported symbols, the struct mirror against the header,
+argument checks that answer before anything is launched, the workspace arithmetic, the float64 helper of the GPU tests against a
+per-element loop, and that helper and the package's NumPy functions against what the reference's own NumPy functions computed
+(tests/golden/layer_norm.npz, made by tests/golden/make_golden_layer_norm.py).  No compute calls here."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+
+import _golden
+import _layer_norm_ref as LR
+import _parity as P
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ARG = -1
+
+
+@pytest.fixture(scope="module")
+def lib():
+    import __graft_entry__ as g
+    g.build()
+    from blocksparse_amd import _lib
+    return _lib
+
+
+def _header():
+    return open(os.path.join(ROOT, "include", "bsmm_norm.h")).read()
+
+
+def test_norm_header_symbols_exported_and_version_unchanged(lib):
+    hdr = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
+    declared = set(re.findall(r"\b(bsmm_[a-z0-9_]+)\s*\(", hdr))
+    assert declared == set(lib.NORM_SYMBOLS), declared ^ set(lib.NORM_SYMBOLS)
+    assert not declared & (set(lib.SYMBOLS) | set(lib.SPARSITY_SYMBOLS) | set(lib.OPTIM_SYMBOLS) | set(lib.OPTIM_LIST_SYMBOLS))
+    L = lib.load()
+    raw = ctypes.CDLL(lib.LIB_PATH)
+    for s in declared:
+        assert hasattr(L, s), s
+        getattr(raw, s)
+    assert L.bsmm_version() == lib.ABI_VERSION == 128
+    import blocksparse_amd
+    assert blocksparse_amd.layer_norm is blocksparse_amd.norms.layer_norm
+    for name in ("layer_norm_fwd", "layer_norm_bwd", "layer_norm_test", "layer_norm_grad_test"):
+        assert callable(getattr(blocksparse_amd.norms, name))
+
+
+def test_struct_mirror_matches_the_header(lib):
+    body = re.search(r"typedef struct bsmm_ln_args \{(.*?)\} bsmm_ln_args;", _header(), flags=re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    ctype = {"int32_t": ctypes.c_int32, "float": ctypes.c_float, "void*": ctypes.c_void_p, "size_t": ctypes.c_size_t}
+    fields = [(m.group(2), ctype[m.group(1)]) for m in re.finditer(r"(int32_t|float|void\*|size_t)\s+(\w+)\s*;", body)]
+    assert [f[0] for f in fields] == ["K", "N", "segments", "axis", "dtype", "relu", "epsilon", "workspace", "workspace_bytes", "stream"]
+    assert [(n, t) for n, t in fields] == [(f[0], f[1]) for f in lib.BsmmLnArgs._fields_]
+    A = lib.BsmmLnArgs
+    # what a C compiler lays out: seven 4-byte members, padding to 8, then three 8-byte members
+    assert [getattr(A, n).offset for n, _ in fields] == [0, 4, 8, 12, 16, 20, 24, 32, 40, 48] and ctypes.sizeof(A) == 56
+
+
+def test_norm_sources_read_no_environment_and_keep_no_state():
+    src = ""
+    for f in ("bsmm_norm.hip", "bsmm_norm_kernels.h"):
+        src += open(os.path.join(ROOT, "blocksparse_amd", "csrc", f)).read()
+    src = re.sub(r"//[^\n]*", "", src)                     # (the comments may say what the code does not do)
+    for word in ("getenv", "hipMalloc", "hipFree", "Synchronize", "atomic", "static int", "static float", "static bool"):
+        assert word not in src, word
+
+
+def _args(lib, K=64, N=16, S=1, axis=0, dtype=2, relu=0, ws=256, ws_bytes=None, backward=0):
+    a = lib.BsmmLnArgs(K=K, N=N, segments=S, axis=axis, dtype=dtype, relu=relu, epsilon=1e-6, workspace=None, workspace_bytes=0, stream=None)
+    if ws_bytes is None:
+        ws_bytes = lib.load().bsmm_layer_norm_workspace_bytes(ctypes.byref(a), backward)
+    a.workspace, a.workspace_bytes = ws, ws_bytes
+    return a
+
+
+def test_argument_checks_answer_before_any_launch(lib):
+    """Every call here is wrong in exactly one way (the addresses are dummies that are never dereferenced), so none may reach a launch."""
+    L = lib.load()
+    one = ctypes.c_void_p(256)
+    fwd = lambda a, x=one, g=one, b=one, y=one, m=one, r=one: L.bsmm_layer_norm(x, g, b, y, m, r, ctypes.byref(a) if a is not None else None)
+    bwd = lambda a, dy=one, x=one, g=one, b=one, m=one, r=one, dx=one, dg=one, db=one: \
+        L.bsmm_layer_norm_grad(dy, x, g, b, m, r, dx, dg, db, ctypes.byref(a) if a is not None else None)
+    for axis in (0, 1):
+        for call, back, names in ((fwd, 0, ("x", "g", "b", "y", "m", "r")), (bwd, 1, ("dy", "x", "g", "b", "m", "r", "dx", "dg", "db"))):
+            ok = dict(axis=axis, backward=back)
+            assert call(None) == ARG
+            for name in names:
+                assert call(_args(lib, **ok), **{name: None}) == ARG, (axis, back, name)
+            assert call(_args(lib, K=0, **ok)) == ARG
+            assert call(_args(lib, N=0, **ok)) == ARG
+            assert call(_args(lib, K=-4, **ok)) == ARG
+            assert call(_args(lib, S=0, **ok)) == ARG
+            assert call(_args(lib, K=64, S=3, **ok)) == ARG            # K % S != 0
+            assert call(_args(lib, dtype=3, **ok)) == ARG
+            assert call(_args(lib, dtype=-1, **ok)) == ARG
+            assert call(_args(lib, relu=2, **ok)) == ARG
+            need = L.bsmm_layer_norm_workspace_bytes(ctypes.byref(_args(lib, **ok)), back)
+            if need:
+                assert call(_args(lib, ws=None, **ok)) == ARG
+                assert call(_args(lib, ws_bytes=need - 1, **ok)) == ARG
+                assert call(_args(lib, ws=258, **ok)) == ARG           # not 4-byte aligned
+            else:
+                assert (axis, back) == (1, 0)                          # the one call that needs no workspace
+    for call, back in ((fwd, 0), (bwd, 1)):
+        assert call(_args(lib, axis=2, backward=back)) == ARG
+        assert call(_args(lib, axis=-1, backward=back)) == ARG
+
+
+def test_workspace_bytes(lib):
+    L = lib.load()
+    wb = lambda back, **kw: L.bsmm_layer_norm_workspace_bytes(ctypes.byref(_args(lib, ws_bytes=0, **kw)), back)
+    assert L.bsmm_layer_norm_workspace_bytes(None, 0) == 0
+    for back in (0, 1):
+        for axis in (0, 1):
+            assert wb(back, K=0, axis=axis) == 0 and wb(back, N=0, axis=axis) == 0 and wb(back, K=-8, N=-8, axis=axis) == 0
+            assert wb(back, S=0, axis=axis) == 0 and wb(back, axis=axis, dtype=9) == 0
+            for dtype in (0, 1, 2):
+                for S in (1, 2):
+                    Ns = list(range(1, 70)) + [96, 255, 256, 257, 511, 512, 513, 1024, 1043, 4096, 8192, 8200, 65536, 1 << 20]
+                    Ks = [S * k for k in list(range(1, 70)) + [511, 512, 1024, 1031, 2048, 2049, 4096, 8192, 8193, 16384, 1 << 17]]
+                    for K in (S * 1, S * 48, S * 2048, S * 2049, S * 8193):
+                        last = 0
+                        for N in Ns:
+                            b = wb(back, K=K, N=N, S=S, axis=axis, dtype=dtype)
+                            assert b >= last and b % 4 == 0, (back, axis, dtype, S, K, N, b, last)
+                            last = b
+                    for N in (1, 24, 64, 513, 8192):
+                        last = 0
+                        for K in Ks:
+                            b = wb(back, K=K, N=N, S=S, axis=axis, dtype=dtype)
+                            assert b >= last, (back, axis, dtype, S, K, N, b, last)
+                            last = b
+    assert wb(0, axis=1) == 0 and wb(1, axis=1) > 0 and wb(0, axis=0) > 0 and wb(1, axis=0) > wb(0, axis=0)
+
+
+def test_python_argument_errors(lib):
+    import torch
+    from blocksparse_amd import layer_norm, norms
+    x, g = torch.zeros(4, 8), torch.ones(8)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        layer_norm(x, g, g)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        norms.layer_norm_fwd(x, g, g)
+
+
+def test_reference_helper_against_a_per_element_loop():
+    rng = np.random.default_rng(5)
+    K, N, S, eps = 12, 5, 3, 1e-3
+    Ks = K // S
+    for axis in (0, 1):
+        for relu in (False, True):
+            x = rng.normal(size=(K, N) if axis == 0 else (N, K))
+            dy = rng.normal(size=x.shape)
+            g, b = rng.normal(size=K), rng.normal(size=K)
+            at = (lambda t, k, n: t[k, n]) if axis == 0 else (lambda t, k, n: t[n, k])
+            mean, rstd = np.zeros((S, N)), np.zeros((S, N))
+            y, dx = np.zeros_like(x), np.zeros_like(x)
+            dg, db = np.zeros(K), np.zeros(K)
+            for s in range(S):
+                ks = range(s * Ks, (s + 1) * Ks)
+                for n in range(N):
+                    vals = [at(x, k, n) for k in ks]
+                    m = sum(vals) / Ks
+                    var = sum((v - m) ** 2 for v in vals) / Ks
+                    r = 1.0 / (var + eps) ** 0.5
+                    mean[s, n], rstd[s, n] = m, r
+                    xh = {k: (at(x, k, n) - m) * r for k in ks}
+                    d = {k: (at(dy, k, n) if (not relu or xh[k] * g[k] + b[k] > 0) else 0.0) for k in ks}
+                    s1 = sum(xh[k] * d[k] * g[k] for k in ks)
+                    s2 = sum(d[k] * g[k] for k in ks)
+                    for k in ks:
+                        pre = xh[k] * g[k] + b[k]
+                        idx = (k, n) if axis == 0 else (n, k)
+                        y[idx] = max(pre, 0.0) if relu else pre
+                        dx[idx] = (d[k] * g[k] - (xh[k] * s1 + s2) / Ks) * r
+                        dg[k] += d[k] * xh[k]
+                        db[k] += d[k]
+            m2, r2 = LR.stats(x, axis, S, eps)
+            np.testing.assert_allclose(m2, mean, rtol=1e-12, atol=1e-14)
+            np.testing.assert_allclose(r2, rstd, rtol=1e-12)
+            np.testing.assert_allclose(LR.forward(x, g, b, axis, S, eps, relu), y, rtol=1e-12, atol=1e-14)
+            dx2, dg2, db2 = LR.backward(dy, x, g, b, axis, S, eps, relu)
+            np.testing.assert_allclose(dx2, dx, rtol=1e-11, atol=1e-13)
+            np.testing.assert_allclose(dg2, dg, rtol=1e-11, atol=1e-13)
+            np.testing.assert_allclose(db2, db, rtol=1e-11, atol=1e-13)
+    # ranks above 2: axis 0 flattens the rest, the last axis flattens the front
+    x3 = rng.normal(size=(6, 2, 5))
+    g6, g5 = rng.normal(size=6), rng.normal(size=5)
+    np.testing.assert_array_equal(LR.forward(x3, g6, g6, 0, 2), LR.forward(x3.reshape(6, 10), g6, g6, 0, 2).reshape(x3.shape))
+    np.testing.assert_array_equal(LR.forward(x3, g5, g5, -1), LR.forward(x3.reshape(12, 5), g5, g5, 1).reshape(x3.shape))
+
+
+def test_helper_and_numpy_functions_agree_with_the_reference_fixture():
+    """L2 <= 1e-5 against the reference's fp32 NumPy results (its own distance from float64 is 4e-8 .. 1.4e-7)."""
+    from blocksparse_amd import norms
+    z = _golden.load("layer_norm")
+    cases = z["cases"]
+    assert len(cases) >= 8
+    seen = set()
+    for i, (K, N, axis, S, relu) in enumerate(cases.tolist()):
+        key = "c%d/" % i
+        X, E, G, B = (z[key + n].astype(np.float32) for n in ("X", "E", "G", "B"))
+        assert X.shape == ((K, N) if axis == 0 else (N, K)) and G.size == K
+        seen.add((axis, S > 1, bool(relu)))
+        want = {n: z[key + n] for n in ("Y", "DX", "DG", "DB")}
+        y = LR.forward(X, G, B, axis, S, 1e-6, bool(relu))
+        dx, dg, db = LR.backward(E, X, G, B, axis, S, 1e-6, bool(relu))
+        y2 = norms.layer_norm_test(X, G, B, axis=axis, segments=S, relu=bool(relu))
+        dx2, dg2, db2 = norms.layer_norm_grad_test(E, X, G, B, axis=axis, segments=S, relu=bool(relu))
+        assert y2.shape == X.shape and dx2.shape == X.shape and dg2.shape == want["DG"].shape and db2.shape == want["DB"].shape
+        for name, got in (("Y", y), ("DX", dx), ("DG", dg), ("DB", db), ("Y", y2), ("DX", dx2), ("DG", dg2), ("DB", db2)):
+            l2, _ = P.errors(np.asarray(got).reshape(-1), want[name].reshape(-1))
+            assert l2 <= 1e-5, (i, name, l2)
+    # both axes, one and several segments on both, relu on and off
+    assert {(a, s) for a, s, _ in seen} == {(0, False), (0, True), (1, False), (1, True)} and {r for _, _, r in seen} == {False, True}
+    shapes = {(int(K), int(N)) for K, N, *_ in cases.tolist()}
+    assert (31, 4) in shapes and (33, 4) in shapes
