@@ -9,6 +9,8 @@ from . import sparsity  # noqa: F401
 from .sparsity import blocksparse_norm, blocksparse_l2_decay, blocksparse_prune  # noqa: F401
 from . import norms  # noqa: F401
 from .norms import layer_norm  # noqa: F401
+from . import ewops  # noqa: F401
+from .ewops import bias_relu, fast_gelu, dropout, bias_dropout, set_entropy  # noqa: F401
 from . import optimize  # noqa: F401
 from .optimize import AdamOptimizer, Ema, PreparedStep, adam_step, ema_step, clip_by_global_norm, global_norm  # noqa: F401
 

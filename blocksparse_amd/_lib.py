@@ -50,6 +50,10 @@ OPTIM_SYMBOLS = ("bsmm_adam", "bsmm_ema", "bsmm_sum_squared", "bsmm_sum_squared_
 OPTIM_LIST_SYMBOLS = ("bsmm_opt_list_bytes", "bsmm_opt_list_build", "bsmm_opt_advance", "bsmm_adam_list", "bsmm_ema_list",
                       "bsmm_sum_squared_list")      # include/bsmm_optim_list.h
 NORM_SYMBOLS = ("bsmm_layer_norm", "bsmm_layer_norm_grad", "bsmm_layer_norm_workspace_bytes")      # include/bsmm_norm.h
+EW_SYMBOLS = ("bsmm_bias_act", "bsmm_bias_act_grad", "bsmm_dropout_mask", "bsmm_dropout_apply", "bsmm_bias_act_dropout",
+              "bsmm_bias_act_dropout_grad", "bsmm_ew_workspace_bytes")      # include/bsmm_ew.h
+ACT_NONE, ACT_RELU, ACT_FAST_GELU = 0, 1, 2
+EW_BIAS_ACT, EW_BIAS_ACT_GRAD, EW_BIAS_ACT_DROPOUT, EW_BIAS_ACT_DROPOUT_GRAD = 0, 1, 2, 3
 BST_SYMBOLS = ("bst_nt", "bst_nn", "bst_tn", "bst_masked_softmax", "bst_softmax_grad", "bst_partial_autoregressive_mask", "bst_nt_softmax", "bst_nt_softmax_grad")
 
 
@@ -127,6 +131,15 @@ class BsmmLnArgs(ctypes.Structure):
     _fields_ = [
         ("K", ctypes.c_int32), ("N", ctypes.c_int32), ("segments", ctypes.c_int32), ("axis", ctypes.c_int32),
         ("dtype", ctypes.c_int32), ("relu", ctypes.c_int32), ("epsilon", ctypes.c_float),
+        ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t), ("stream", ctypes.c_void_p),
+    ]
+
+
+class BsmmEwArgs(ctypes.Structure):
+    """Mirror of ``struct bsmm_ew_args`` (include/bsmm_ew.h)."""
+    _fields_ = [
+        ("K", ctypes.c_int32), ("N", ctypes.c_int32), ("axis", ctypes.c_int32), ("dtype", ctypes.c_int32),
+        ("act", ctypes.c_int32), ("generate", ctypes.c_int32), ("threshold", ctypes.c_int32), ("scale", ctypes.c_float),
         ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t), ("stream", ctypes.c_void_p),
     ]
 
@@ -300,6 +313,18 @@ def load():
     lib.bsmm_layer_norm_grad.restype = ctypes.c_int
     lib.bsmm_layer_norm_workspace_bytes.argtypes = [pln, i32]
     lib.bsmm_layer_norm_workspace_bytes.restype = ctypes.c_size_t
+    # include/bsmm_ew.h
+    pew = ctypes.POINTER(BsmmEwArgs)
+    lib.bsmm_bias_act.argtypes = [vp, vp, vp, pew]
+    lib.bsmm_bias_act_grad.argtypes = [vp, vp, vp, vp, vp, pew]
+    lib.bsmm_dropout_mask.argtypes = [vp, vp, ctypes.c_int64, i32, vp]
+    lib.bsmm_dropout_apply.argtypes = [vp, vp, vp, ctypes.c_int64, f32, i32, vp]
+    lib.bsmm_bias_act_dropout.argtypes = [vp, vp, vp, vp, vp, vp, pew]
+    lib.bsmm_bias_act_dropout_grad.argtypes = [vp, vp, vp, vp, vp, vp, pew]
+    for name in EW_SYMBOLS:
+        getattr(lib, name).restype = ctypes.c_int
+    lib.bsmm_ew_workspace_bytes.argtypes = [pew, i32]
+    lib.bsmm_ew_workspace_bytes.restype = ctypes.c_size_t
     if lib.bsmm_version() != ABI_VERSION:
         raise RuntimeError("blocksparse_amd: %s reports ABI version %d, this binding expects %d -- rebuild the library "
                            "(python -c 'import __graft_entry__ as g; g.build()')" % (LIB_PATH, lib.bsmm_version(), ABI_VERSION))
