@@ -11,6 +11,10 @@ from . import norms  # noqa: F401
 from .norms import layer_norm  # noqa: F401
 from . import ewops  # noqa: F401
 from .ewops import bias_relu, fast_gelu, dropout, bias_dropout, set_entropy  # noqa: F401
+from . import embed  # noqa: F401
+from .embed import embedding_lookup  # noqa: F401
+from . import xent  # noqa: F401
+from .xent import softmax_cross_entropy  # noqa: F401
 from . import optimize  # noqa: F401
 from .optimize import AdamOptimizer, Ema, PreparedStep, adam_step, ema_step, clip_by_global_norm, global_norm  # noqa: F401
 

@@ -54,6 +54,13 @@ EW_SYMBOLS = ("bsmm_bias_act", "bsmm_bias_act_grad", "bsmm_dropout_mask", "bsmm_
               "bsmm_bias_act_dropout_grad", "bsmm_ew_workspace_bytes")      # include/bsmm_ew.h
 ACT_NONE, ACT_RELU, ACT_FAST_GELU = 0, 1, 2
 EW_BIAS_ACT, EW_BIAS_ACT_GRAD, EW_BIAS_ACT_DROPOUT, EW_BIAS_ACT_DROPOUT_GRAD = 0, 1, 2, 3
+ENDS_SYMBOLS = ("bsmm_xent_fwd", "bsmm_xent_bwd", "bsmm_xent_path", "bsmm_embed_fwd", "bsmm_embed_grad",
+                "bsmm_ends_workspace_bytes")      # include/bsmm_ends.h
+XENT_F16_SCALE = 32768.0
+XENT_SHORT, XENT_REG, XENT_REG_WIDE, XENT_LONG, XENT_VEC, XENT_STRIDED = 1, 2, 3, 4, 256, 512
+XENT_SHORT_MAX, XENT_REG_MAX, XENT_WIDE_MAX, XENT_MAX_GRID = 1024, 8192, 32768, 2048
+EMBED_CHUNK = 128
+ENDS_XENT_FWD, ENDS_XENT_BWD, ENDS_EMBED_FWD, ENDS_EMBED_GRAD = 0, 1, 2, 3
 BST_SYMBOLS = ("bst_nt", "bst_nn", "bst_tn", "bst_masked_softmax", "bst_softmax_grad", "bst_partial_autoregressive_mask", "bst_nt_softmax", "bst_nt_softmax_grad")
 
 
@@ -140,6 +147,24 @@ class BsmmEwArgs(ctypes.Structure):
     _fields_ = [
         ("K", ctypes.c_int32), ("N", ctypes.c_int32), ("axis", ctypes.c_int32), ("dtype", ctypes.c_int32),
         ("act", ctypes.c_int32), ("generate", ctypes.c_int32), ("threshold", ctypes.c_int32), ("scale", ctypes.c_float),
+        ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t), ("stream", ctypes.c_void_p),
+    ]
+
+
+class BsmmXentArgs(ctypes.Structure):
+    """Mirror of ``struct bsmm_xent_args`` (include/bsmm_ends.h)."""
+    _fields_ = [
+        ("x", ctypes.c_void_p), ("labels", ctypes.c_void_p), ("loss", ctypes.c_void_p), ("g", ctypes.c_void_p),
+        ("dy", ctypes.c_void_p), ("dx", ctypes.c_void_p),
+        ("N", ctypes.c_int32), ("K", ctypes.c_int32), ("dtype", ctypes.c_int32), ("reserved", ctypes.c_int32),
+        ("stream", ctypes.c_void_p),
+    ]
+
+
+class BsmmEmbedArgs(ctypes.Structure):
+    """Mirror of ``struct bsmm_embed_args`` (include/bsmm_ends.h)."""
+    _fields_ = [
+        ("C", ctypes.c_int32), ("K", ctypes.c_int32), ("nIdx", ctypes.c_int32), ("dtype", ctypes.c_int32),
         ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t), ("stream", ctypes.c_void_p),
     ]
 
@@ -325,6 +350,17 @@ def load():
         getattr(lib, name).restype = ctypes.c_int
     lib.bsmm_ew_workspace_bytes.argtypes = [pew, i32]
     lib.bsmm_ew_workspace_bytes.restype = ctypes.c_size_t
+    # include/bsmm_ends.h
+    pxe, pem = ctypes.POINTER(BsmmXentArgs), ctypes.POINTER(BsmmEmbedArgs)
+    lib.bsmm_xent_fwd.argtypes = [pxe]
+    lib.bsmm_xent_bwd.argtypes = [pxe]
+    lib.bsmm_xent_path.argtypes = [pxe]
+    lib.bsmm_embed_fwd.argtypes = [vp, vp, vp, pem]
+    lib.bsmm_embed_grad.argtypes = [vp, vp, vp, vp, pem]
+    for name in ENDS_SYMBOLS:
+        getattr(lib, name).restype = ctypes.c_int
+    lib.bsmm_ends_workspace_bytes.argtypes = [pem, i32]
+    lib.bsmm_ends_workspace_bytes.restype = ctypes.c_size_t
     if lib.bsmm_version() != ABI_VERSION:
         raise RuntimeError("blocksparse_amd: %s reports ABI version %d, this binding expects %d -- rebuild the library "
                            "(python -c 'import __graft_entry__ as g; g.build()')" % (LIB_PATH, lib.bsmm_version(), ABI_VERSION))
