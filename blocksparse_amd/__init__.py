@@ -15,6 +15,8 @@ from . import embed  # noqa: F401
 from .embed import embedding_lookup  # noqa: F401
 from . import xent  # noqa: F401
 from .xent import softmax_cross_entropy  # noqa: F401
+from . import lstm  # noqa: F401
+from .lstm import fused_lstm_gates  # noqa: F401
 from . import optimize  # noqa: F401
 from .optimize import AdamOptimizer, Ema, PreparedStep, adam_step, ema_step, clip_by_global_norm, global_norm  # noqa: F401
 

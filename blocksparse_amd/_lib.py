@@ -61,6 +61,7 @@ XENT_SHORT, XENT_REG, XENT_REG_WIDE, XENT_LONG, XENT_VEC, XENT_STRIDED = 1, 2, 3
 XENT_SHORT_MAX, XENT_REG_MAX, XENT_WIDE_MAX, XENT_MAX_GRID = 1024, 8192, 32768, 2048
 EMBED_CHUNK = 128
 ENDS_XENT_FWD, ENDS_XENT_BWD, ENDS_EMBED_FWD, ENDS_EMBED_GRAD = 0, 1, 2, 3
+LSTM_SYMBOLS = ("bsmm_lstm_gates", "bsmm_lstm_gates_grad")      # include/bsmm_lstm.h
 BST_SYMBOLS = ("bst_nt", "bst_nn", "bst_tn", "bst_masked_softmax", "bst_softmax_grad", "bst_partial_autoregressive_mask", "bst_nt_softmax", "bst_nt_softmax_grad")
 
 
@@ -166,6 +167,14 @@ class BsmmEmbedArgs(ctypes.Structure):
     _fields_ = [
         ("C", ctypes.c_int32), ("K", ctypes.c_int32), ("nIdx", ctypes.c_int32), ("dtype", ctypes.c_int32),
         ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t), ("stream", ctypes.c_void_p),
+    ]
+
+
+class BsmmLstmArgs(ctypes.Structure):
+    """Mirror of ``struct bsmm_lstm_args`` (include/bsmm_lstm.h)."""
+    _fields_ = [
+        ("K", ctypes.c_int32), ("N", ctypes.c_int32), ("axis", ctypes.c_int32), ("dtype", ctypes.c_int32),
+        ("gate_ld", ctypes.c_int64), ("dgate_ld", ctypes.c_int64), ("forget_bias", ctypes.c_float), ("stream", ctypes.c_void_p),
     ]
 
 
@@ -361,6 +370,12 @@ def load():
         getattr(lib, name).restype = ctypes.c_int
     lib.bsmm_ends_workspace_bytes.argtypes = [pem, i32]
     lib.bsmm_ends_workspace_bytes.restype = ctypes.c_size_t
+    # include/bsmm_lstm.h
+    plstm = ctypes.POINTER(BsmmLstmArgs)
+    lib.bsmm_lstm_gates.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, plstm]
+    lib.bsmm_lstm_gates_grad.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, plstm]
+    for name in LSTM_SYMBOLS:
+        getattr(lib, name).restype = ctypes.c_int
     if lib.bsmm_version() != ABI_VERSION:
         raise RuntimeError("blocksparse_amd: %s reports ABI version %d, this binding expects %d -- rebuild the library "
                            "(python -c 'import __graft_entry__ as g; g.build()')" % (LIB_PATH, lib.bsmm_version(), ABI_VERSION))
