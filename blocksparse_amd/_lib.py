@@ -391,6 +391,12 @@ def dw_layout(world, rank, blocks, bsize):
     return int(sh.value), int(lo.value), int(hi.value), int(cap.value)
 
 
+def dtype_code(dtype):
+    """The BSMM_F32 / BSMM_F16 / BSMM_BF16 code of a torch dtype, None for any other dtype: each caller raises its own error."""
+    import torch
+    return {torch.float32: F32, torch.float16: F16, torch.bfloat16: BF16}.get(dtype)
+
+
 def error_string(code):
     return load().bsmm_error_string(int(code)).decode()
 

@@ -7,6 +7,7 @@
 #include <cstdint>
 
 #include "bsmm.h"
+#include "bsmm_host.h"
 #include "bsmm_plan.h"
 #include "bsmm_l2norm.h"
 #include "bsmm_sparse_proj.h"
@@ -87,8 +88,6 @@ int check_common(const bsmm_args* a) {
     if (reinterpret_cast<uintptr_t>(a->lut) & 15) return BSMM_ERR_ARG;
     return BSMM_OK;
 }
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // A plan must be one this library built for THIS kind of call (the descriptor comes from bsmm_plan_attach): anything else
 // is refused here, on the host, instead of reaching a kernel that would not recognise it.

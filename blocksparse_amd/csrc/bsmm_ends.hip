@@ -4,23 +4,13 @@
 
 #include "bsmm_ends.h"
 #include "bsmm_ends_kernels.h"
+#include "bsmm_host.h"
 
 using namespace bsmm;
 
 namespace {
 
-inline bool dtype_ok(int dtype) { return dtype == BSMM_F32 || dtype == BSMM_F16 || dtype == BSMM_BF16; }
 inline size_t elem_bytes(int dtype) { return dtype == BSMM_F32 ? 4 : 2; }
-inline bool aligned_to(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-inline bool aligned16(const void* p) { return aligned_to(p, 16); }
-inline unsigned capped(unsigned long long units) { return (unsigned)(units < (unsigned long long)ENDS_MAX_GRID ? units : ENDS_MAX_GRID); }
-inline bool product_ok(int a, int b) { return (long long)a * (long long)b < (1ll << 31); }
-
-#define ENDS_LAUNCH(KERNEL, GRID, BLOCK, ...)                          \
-    do {                                                               \
-        KERNEL<<<(GRID), (BLOCK), 0, st>>>(__VA_ARGS__);               \
-        if (int rc_ = (int)hipGetLastError()) return rc_;              \
-    } while (0)
 
 // ---- softmax cross-entropy ----------------------------------------------------------------------------------------------------------
 int xent_check(const bsmm_xent_args* a) {
@@ -60,25 +50,25 @@ int xent_forward(const bsmm_xent_args* a, int path) {
     const int units = (K + V - 1) / V;
     switch (path & 0xff) {
         case BSMM_XENT_SHORT: {
-            const unsigned grid = capped(((unsigned long long)N + 3) / 4);
+            const unsigned grid = capped(((unsigned long long)N + 3) / 4, ENDS_MAX_GRID);
             // units a lane holds: 1 or 2 on the 16-byte path (K <= 512, <= 1024), 4 or 16 on the element path (K <= 256, <= 1024)
             if constexpr (V == 8) {
-                if (units <= 64) ENDS_LAUNCH((xent_rows_kernel<DT, 8, 1, 64>), grid, 256, x, a->labels, a->loss, g, N, K, gscale);
-                else ENDS_LAUNCH((xent_rows_kernel<DT, 8, 2, 64>), grid, 256, x, a->labels, a->loss, g, N, K, gscale);
+                if (units <= 64) BSMM_LAUNCH((xent_rows_kernel<DT, 8, 1, 64>), grid, 256, st, x, a->labels, a->loss, g, N, K, gscale);
+                else BSMM_LAUNCH((xent_rows_kernel<DT, 8, 2, 64>), grid, 256, st, x, a->labels, a->loss, g, N, K, gscale);
             } else {
-                if (units <= 256) ENDS_LAUNCH((xent_rows_kernel<DT, 1, 4, 64>), grid, 256, x, a->labels, a->loss, g, N, K, gscale);
-                else ENDS_LAUNCH((xent_rows_kernel<DT, 1, 16, 64>), grid, 256, x, a->labels, a->loss, g, N, K, gscale);
+                if (units <= 256) BSMM_LAUNCH((xent_rows_kernel<DT, 1, 4, 64>), grid, 256, st, x, a->labels, a->loss, g, N, K, gscale);
+                else BSMM_LAUNCH((xent_rows_kernel<DT, 1, 16, 64>), grid, 256, st, x, a->labels, a->loss, g, N, K, gscale);
             }
             break;
         }
         case BSMM_XENT_REG:
-            ENDS_LAUNCH((xent_rows_kernel<DT, V, (V == 8 ? 4 : 16), 256>), capped(N), 256, x, a->labels, a->loss, g, N, K, gscale);
+            BSMM_LAUNCH((xent_rows_kernel<DT, V, (V == 8 ? 4 : 16), 256>), capped(N, ENDS_MAX_GRID), 256, st, x, a->labels, a->loss, g, N, K, gscale);
             break;
         case BSMM_XENT_REG_WIDE:
-            ENDS_LAUNCH((xent_rows_kernel<DT, V, (V == 8 ? 4 : 16), 1024>), capped(N), 1024, x, a->labels, a->loss, g, N, K, gscale);
+            BSMM_LAUNCH((xent_rows_kernel<DT, V, (V == 8 ? 4 : 16), 1024>), capped(N, ENDS_MAX_GRID), 1024, st, x, a->labels, a->loss, g, N, K, gscale);
             break;
         default:
-            ENDS_LAUNCH((xent_long_kernel<DT, V>), capped(N), 1024, x, a->labels, a->loss, g, N, K, gscale);
+            BSMM_LAUNCH((xent_long_kernel<DT, V>), capped(N, ENDS_MAX_GRID), 1024, st, x, a->labels, a->loss, g, N, K, gscale);
             break;
     }
     return BSMM_OK;
@@ -90,7 +80,7 @@ int xent_backward(const bsmm_xent_args* a) {
     hipStream_t st = static_cast<hipStream_t>(a->stream);
     const uint32_t upr = (uint32_t)(a->K / V), units = (uint32_t)a->N * upr;
     const float unscale = a->dtype == BSMM_F16 ? 1.f / BSMM_XENT_F16_SCALE : 1.f;
-    ENDS_LAUNCH((xent_bwd_kernel<DT, V>), capped(((unsigned long long)units + 255) / 256), 256, static_cast<const T*>(a->g), a->dy,
+    BSMM_LAUNCH((xent_bwd_kernel<DT, V>), capped(((unsigned long long)units + 255) / 256, ENDS_MAX_GRID), 256, st, static_cast<const T*>(a->g), a->dy,
                 static_cast<T*>(a->dx), units, upr, unscale);
     return BSMM_OK;
 }
@@ -116,9 +106,9 @@ int embed_backward(const void* dyv, const int32_t* idx, const int32_t* order, fl
     const int K = a->K, KU = (K + V - 1) / V, CT = embed_team(KU), tiles = (KU + CT - 1) / CT, teams = 256 / CT;
     const unsigned long long items1 = (unsigned long long)embed_chunks(a->nIdx) * tiles, items2 = (unsigned long long)a->C * tiles;
     if (items1 >= (1ull << 32) || items2 >= (1ull << 32)) return BSMM_ERR_ARG;
-    ENDS_LAUNCH((embed_grad_chunks_kernel<DT, V>), capped((items1 + teams - 1) / teams), 256, static_cast<const T*>(dyv), idx, order, dw, ws,
+    BSMM_LAUNCH((embed_grad_chunks_kernel<DT, V>), capped((items1 + teams - 1) / teams, ENDS_MAX_GRID), 256, st, static_cast<const T*>(dyv), idx, order, dw, ws,
                 a->C, K, a->nIdx, CT, tiles, (uint32_t)items1);
-    ENDS_LAUNCH((embed_grad_merge_kernel<V>), capped((items2 + teams - 1) / teams), 256, idx, order, dw, ws, a->C, K, a->nIdx, CT, tiles,
+    BSMM_LAUNCH((embed_grad_merge_kernel<V>), capped((items2 + teams - 1) / teams, ENDS_MAX_GRID), 256, st, idx, order, dw, ws, a->C, K, a->nIdx, CT, tiles,
                 (uint32_t)items2);
     return BSMM_OK;
 }
@@ -139,11 +129,7 @@ int bsmm_xent_fwd(const bsmm_xent_args* args) {
     if (!aligned_to(args->x, es) || !aligned_to(args->g, es) || !aligned_to(args->labels, 4) || !aligned_to(args->loss, 4)) return BSMM_ERR_ARG;
     const int path = xent_path(args);
     const bool vec = (path & BSMM_XENT_VEC) != 0;
-    switch (args->dtype) {
-        case BSMM_F32: return vec ? xent_forward<DTf32, 8>(args, path) : xent_forward<DTf32, 1>(args, path);
-        case BSMM_F16: return vec ? xent_forward<DTf16, 8>(args, path) : xent_forward<DTf16, 1>(args, path);
-        default: return vec ? xent_forward<DTbf16, 8>(args, path) : xent_forward<DTbf16, 1>(args, path);
-    }
+    return with_dtype(args->dtype, vec, [&](auto dt, auto wide) { return xent_forward<decltype(dt), (wide ? 8 : 1)>(args, path); });
 }
 
 int bsmm_xent_bwd(const bsmm_xent_args* args) {
@@ -152,11 +138,7 @@ int bsmm_xent_bwd(const bsmm_xent_args* args) {
     const size_t es = elem_bytes(args->dtype);
     if (!aligned_to(args->g, es) || !aligned_to(args->dx, es) || !aligned_to(args->dy, 4)) return BSMM_ERR_ARG;
     const bool vec = aligned16(args->g) && aligned16(args->dx) && args->K % 8 == 0;
-    switch (args->dtype) {
-        case BSMM_F32: return vec ? xent_backward<DTf32, 8>(args) : xent_backward<DTf32, 1>(args);
-        case BSMM_F16: return vec ? xent_backward<DTf16, 8>(args) : xent_backward<DTf16, 1>(args);
-        default: return vec ? xent_backward<DTbf16, 8>(args) : xent_backward<DTbf16, 1>(args);
-    }
+    return with_dtype(args->dtype, vec, [&](auto dt, auto wide) { return xent_backward<decltype(dt), (wide ? 8 : 1)>(args); });
 }
 
 size_t bsmm_ends_workspace_bytes(const bsmm_embed_args* args, int32_t which) {
@@ -172,15 +154,15 @@ int bsmm_embed_fwd(const void* w, const int32_t* idx, void* y, const bsmm_embed_
     hipStream_t st = static_cast<hipStream_t>(args->stream);
     if (aligned16(w) && aligned16(y) && row_bytes % 16 == 0) {
         const uint32_t upr = (uint32_t)(row_bytes / 16), units = (uint32_t)args->nIdx * upr;
-        ENDS_LAUNCH(embed_fwd_kernel<uint4>, capped(((unsigned long long)units + 255) / 256), 256, static_cast<const uint4*>(w), idx,
+        BSMM_LAUNCH(embed_fwd_kernel<uint4>, capped(((unsigned long long)units + 255) / 256, ENDS_MAX_GRID), 256, st, static_cast<const uint4*>(w), idx,
                     static_cast<uint4*>(y), args->C, upr, units);
     } else if (es == 4) {
         const uint32_t upr = (uint32_t)args->K, units = (uint32_t)args->nIdx * upr;
-        ENDS_LAUNCH(embed_fwd_kernel<uint32_t>, capped(((unsigned long long)units + 255) / 256), 256, static_cast<const uint32_t*>(w), idx,
+        BSMM_LAUNCH(embed_fwd_kernel<uint32_t>, capped(((unsigned long long)units + 255) / 256, ENDS_MAX_GRID), 256, st, static_cast<const uint32_t*>(w), idx,
                     static_cast<uint32_t*>(y), args->C, upr, units);
     } else {
         const uint32_t upr = (uint32_t)args->K, units = (uint32_t)args->nIdx * upr;
-        ENDS_LAUNCH(embed_fwd_kernel<uint16_t>, capped(((unsigned long long)units + 255) / 256), 256, static_cast<const uint16_t*>(w), idx,
+        BSMM_LAUNCH(embed_fwd_kernel<uint16_t>, capped(((unsigned long long)units + 255) / 256, ENDS_MAX_GRID), 256, st, static_cast<const uint16_t*>(w), idx,
                     static_cast<uint16_t*>(y), args->C, upr, units);
     }
     return BSMM_OK;
@@ -194,11 +176,7 @@ int bsmm_embed_grad(const void* dy, const int32_t* idx, const int32_t* order, fl
     if (args->workspace == nullptr || !aligned_to(args->workspace, 4) || args->workspace_bytes < embed_grad_floats(args) * sizeof(float))
         return BSMM_ERR_ARG;
     const bool vec = aligned16(dy) && aligned16(dw) && aligned16(args->workspace) && args->K % 8 == 0;
-    switch (args->dtype) {
-        case BSMM_F32: return vec ? embed_backward<DTf32, 8>(dy, idx, order, dw, args) : embed_backward<DTf32, 1>(dy, idx, order, dw, args);
-        case BSMM_F16: return vec ? embed_backward<DTf16, 8>(dy, idx, order, dw, args) : embed_backward<DTf16, 1>(dy, idx, order, dw, args);
-        default: return vec ? embed_backward<DTbf16, 8>(dy, idx, order, dw, args) : embed_backward<DTbf16, 1>(dy, idx, order, dw, args);
-    }
+    return with_dtype(args->dtype, vec, [&](auto dt, auto wide) { return embed_backward<decltype(dt), (wide ? 8 : 1)>(dy, idx, order, dw, args); });
 }
 
 }  // extern "C"

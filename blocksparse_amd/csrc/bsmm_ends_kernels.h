@@ -1,6 +1,6 @@
 // bsmm_ends_kernels.h -- kernels behind include/bsmm_ends.h: softmax cross-entropy and the embedding lookup with its sorted gradient.  All of
 // them are memory bound.  A UNIT is V consecutive elements of a row that one lane moves with one access: V = 8 on the 16-byte path (16 bytes
-// of a 16-bit type, two 16-byte accesses of fp32), V = 1 on the element path.
+// of a 16-bit type, two 16-byte accesses of fp32), V = 1 on the element path (vec_load / vec_store of bsmm_vec.h, the wave reductions too).
 //
 //   xent_rows_kernel<V, R, NT>   rows that stay in registers: a team of NT lanes (64: a wave, four rows per workgroup, shuffles only; 256 or
 //                                1024: the workgroup, sums of the waves meet in LDS) holds R units per lane.  One read of x, one write of g.
@@ -13,8 +13,8 @@
 // x and g (and g and dx) may be the SAME pointer: none of them is declared __restrict__, a lane stores a unit only after it has read it, and a
 // row is stored only after the whole row has been read (registers) or re-read unit by unit (long rows).
 #pragma once
-#include "bsmm_common.h"
 #include "bsmm_ends.h"
+#include "bsmm_vec.h"
 
 // every sum below is a chain of separate fp32 additions in a fixed order
 #pragma clang fp contract(off)
@@ -26,77 +26,11 @@ constexpr int ENDS_MAX_GRID = BSMM_XENT_MAX_GRID;
 constexpr int EMBED_CHUNK = BSMM_EMBED_CHUNK;
 constexpr int EMBED_BATCH = 4;         // rows of dy a lane has in flight
 
-// ---- V consecutive elements <-> V floats (V = 8: p 16-byte aligned) ----
-template <class DT, int V>
-__device__ __forceinline__ void ends_load(const typename DT::T* p, float* v) {
-    if constexpr (V == 1) {
-        v[0] = DT::to_f32(p[0]);
-    } else if constexpr (!DT::is16) {
-        const float4 a = reinterpret_cast<const float4*>(p)[0], c = reinterpret_cast<const float4*>(p)[1];
-        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = c.x; v[5] = c.y; v[6] = c.z; v[7] = c.w;
-    } else {
-        const uint4 q = *reinterpret_cast<const uint4*>(p);
-        const uint32_t wd[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            v[2 * j] = DT::to_f32((uint16_t)(wd[j] & 0xffffu));
-            v[2 * j + 1] = DT::to_f32((uint16_t)(wd[j] >> 16));
-        }
-    }
-}
-
-template <class DT, int V>
-__device__ __forceinline__ void ends_store(typename DT::T* p, const float* v) {
-    if constexpr (V == 1) {
-        p[0] = DT::from_f32(v[0]);
-    } else if constexpr (!DT::is16) {
-        reinterpret_cast<float4*>(p)[0] = make_float4(v[0], v[1], v[2], v[3]);
-        reinterpret_cast<float4*>(p)[1] = make_float4(v[4], v[5], v[6], v[7]);
-    } else {
-        uint32_t wd[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) wd[j] = (uint32_t)DT::from_f32(v[2 * j]) | ((uint32_t)DT::from_f32(v[2 * j + 1]) << 16);
-        *reinterpret_cast<uint4*>(p) = make_uint4(wd[0], wd[1], wd[2], wd[3]);
-    }
-}
-
-template <int V>
-__device__ __forceinline__ void ends_store_f32(float* p, const float* v) {
-    if constexpr (V == 1) {
-        p[0] = v[0];
-    } else {
-        reinterpret_cast<float4*>(p)[0] = make_float4(v[0], v[1], v[2], v[3]);
-        reinterpret_cast<float4*>(p)[1] = make_float4(v[4], v[5], v[6], v[7]);
-    }
-}
-
-template <int V>
-__device__ __forceinline__ void ends_load_f32(const float* p, float* v) {
-    if constexpr (V == 1) {
-        v[0] = p[0];
-    } else {
-        const float4 a = reinterpret_cast<const float4*>(p)[0], c = reinterpret_cast<const float4*>(p)[1];
-        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = c.x; v[5] = c.y; v[6] = c.z; v[7] = c.w;
-    }
-}
-
 // ---- reductions over a team of NT lanes; every lane gets the result.  NT = 64: shuffles only.  NT > 64: the waves' values meet in LDS and
 // every lane adds them in ascending wave order.  `lds` holds NT / 64 floats and is free again when the call returns. ----
-__device__ __forceinline__ float ends_wave_max(float v) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
-    return v;
-}
-
-__device__ __forceinline__ float ends_wave_sum(float v) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
 template <int NT>
 __device__ __forceinline__ float ends_team_max(float v, float* lds) {
-    v = ends_wave_max(v);
+    v = wave_max(v);
     if constexpr (NT > 64) {
         const int wave = threadIdx.x >> 6;
         if ((threadIdx.x & 63) == 0) lds[wave] = v;
@@ -111,7 +45,7 @@ __device__ __forceinline__ float ends_team_max(float v, float* lds) {
 
 template <int NT>
 __device__ __forceinline__ float ends_team_sum(float v, float* lds) {
-    v = ends_wave_sum(v);
+    v = wave_sum(v);
     if constexpr (NT > 64) {
         const int wave = threadIdx.x >> 6;
         if ((threadIdx.x & 63) == 0) lds[wave] = v;
@@ -136,7 +70,7 @@ __device__ __forceinline__ void xent_row_in_registers(const typename DT::T* xr, 
         float z[V];
 #pragma unroll
         for (int e = 0; e < V; ++e) z[e] = 0.f;
-        for (int u = t; u < units; u += NT) ends_store<DT, V>(gr + (size_t)u * V, z);
+        for (int u = t; u < units; u += NT) vec_store<DT, V>(gr + (size_t)u * V, z);
         if (t == 0) *loss_row = 0.f;
         return;
     }
@@ -150,7 +84,7 @@ __device__ __forceinline__ void xent_row_in_registers(const typename DT::T* xr, 
 #pragma unroll
     for (int j = 0; j < R; ++j) {
         // a unit past the row reads the row's last unit again: a valid address, the maximum is unchanged, and the sum below leaves it out
-        ends_load<DT, V>(xr + (size_t)min(t + j * NT, units - 1) * V, &v[j * V]);
+        vec_load<DT, V>(xr + (size_t)min(t + j * NT, units - 1) * V, &v[j * V]);
 #pragma unroll
         for (int e = 0; e < V; ++e) m = fmaxf(m, v[j * V + e]);
     }
@@ -177,7 +111,7 @@ __device__ __forceinline__ void xent_row_in_registers(const typename DT::T* xr, 
             float o[V];
 #pragma unroll
             for (int e = 0; e < V; ++e) o[e] = (v[j * V + e] * inv) * gscale;
-            ends_store<DT, V>(gr + (size_t)u * V, o);
+            vec_store<DT, V>(gr + (size_t)u * V, o);
         }
     }
     // the label's element, by the lane that has just stored its unit (stores of one lane to one address keep their order)
@@ -214,7 +148,7 @@ __global__ void __launch_bounds__(1024) xent_long_kernel(const typename DT::T* x
             float z[V];
 #pragma unroll
             for (int e = 0; e < V; ++e) z[e] = 0.f;
-            for (int u = t; u < units; u += NT) ends_store<DT, V>(gr + (size_t)u * V, z);
+            for (int u = t; u < units; u += NT) vec_store<DT, V>(gr + (size_t)u * V, z);
             if (t == 0) loss[row] = 0.f;
             continue;
         }
@@ -224,7 +158,7 @@ __global__ void __launch_bounds__(1024) xent_long_kernel(const typename DT::T* x
         float m = -INFINITY, others = 0.f;               // others: the sum without the label's term (see xent_row_in_registers)
         for (int u = t; u < units; u += NT) {
             float v[V];
-            ends_load<DT, V>(xr + (size_t)u * V, v);
+            vec_load<DT, V>(xr + (size_t)u * V, v);
             float mu = v[0];
 #pragma unroll
             for (int e = 0; e < V; ++e) mu = fmaxf(mu, v[e]);
@@ -243,10 +177,10 @@ __global__ void __launch_bounds__(1024) xent_long_kernel(const typename DT::T* x
         const float inv = 1.f / s;
         for (int u = t; u < units; u += NT) {
             float v[V];
-            ends_load<DT, V>(xr + (size_t)u * V, v);
+            vec_load<DT, V>(xr + (size_t)u * V, v);
 #pragma unroll
             for (int e = 0; e < V; ++e) v[e] = (exp2f((v[e] - M) * ENDS_LOG2E) * inv) * gscale;
-            ends_store<DT, V>(gr + (size_t)u * V, v);
+            vec_store<DT, V>(gr + (size_t)u * V, v);
         }
         if (t == (label / V) % NT) gr[label] = DT::from_f32(-(others * inv) * gscale);
     }
@@ -259,10 +193,10 @@ __global__ void __launch_bounds__(256) xent_bwd_kernel(const typename DT::T* g, 
     for (uint32_t u = blockIdx.x * 256u + threadIdx.x; u < units; u += gridDim.x * 256u) {
         const float d = dy[u / upr];
         float v[V];
-        ends_load<DT, V>(g + (size_t)u * V, v);
+        vec_load<DT, V>(g + (size_t)u * V, v);
 #pragma unroll
         for (int e = 0; e < V; ++e) v[e] = (v[e] * unscale) * d;
-        ends_store<DT, V>(dx + (size_t)u * V, v);
+        vec_store<DT, V>(dx + (size_t)u * V, v);
     }
 }
 
@@ -319,14 +253,14 @@ __global__ void __launch_bounds__(256) embed_grad_chunks_kernel(const typename D
             for (int b = 0; b < EMBED_BATCH; ++b) {
                 if (p + b < p1) {
                     kk[b] = embed_key(idx, order, nIdx, p + b, &r);
-                    ends_load<DT, V>(dy + (size_t)r * K + col, vv[b]);
+                    vec_load<DT, V>(dy + (size_t)r * K + col, vv[b]);
                 }
             }
 #pragma unroll
             for (int b = 0; b < EMBED_BATCH; ++b) {
                 if (p + b < p1) {
                     if (kk[b] != cur) {                  // a run ends inside the chunk
-                        if ((unsigned)cur < (unsigned)C) ends_store_f32<V>(before ? ws + (size_t)(2 * j) * K + col : dw + (size_t)cur * K + col, acc);
+                        if ((unsigned)cur < (unsigned)C) vec_store_f32<V>(before ? ws + (size_t)(2 * j) * K + col : dw + (size_t)cur * K + col, acc);
                         before = false;
                         cur = kk[b];
 #pragma unroll
@@ -340,7 +274,7 @@ __global__ void __launch_bounds__(256) embed_grad_chunks_kernel(const typename D
         if ((unsigned)cur < (unsigned)C) {
             const bool behind = p1 < nIdx && embed_key(idx, order, nIdx, p1, &r) == cur;
             float* out = before ? ws + (size_t)(2 * j) * K + col : (behind ? ws + (size_t)(2 * j + 1) * K + col : dw + (size_t)cur * K + col);
-            ends_store_f32<V>(out, acc);
+            vec_store_f32<V>(out, acc);
         }
     }
 }
@@ -378,15 +312,15 @@ __global__ void __launch_bounds__(256) embed_grad_merge_kernel(const int32_t* __
         if (hi > lo) {
             const int jl = lo / EMBED_CHUNK, jh = (hi - 1) / EMBED_CHUNK;
             if (jl == jh) continue;
-            ends_load_f32<V>(ws + (size_t)(2 * jl + 1) * K + col, acc);
+            vec_load_f32<V>(ws + (size_t)(2 * jl + 1) * K + col, acc);
             for (int j = jl + 1; j <= jh; ++j) {
                 float v[V];
-                ends_load_f32<V>(ws + (size_t)(2 * j) * K + col, v);
+                vec_load_f32<V>(ws + (size_t)(2 * j) * K + col, v);
 #pragma unroll
                 for (int e = 0; e < V; ++e) acc[e] += v[e];
             }
         }
-        ends_store_f32<V>(dw + (size_t)c * K + col, acc);
+        vec_store_f32<V>(dw + (size_t)c * K + col, acc);
     }
 }
 

@@ -4,15 +4,11 @@
 
 #include "bsmm_ew.h"
 #include "bsmm_ew_kernels.h"
+#include "bsmm_host.h"
 
 using namespace bsmm;
 
 namespace {
-
-inline bool dtype_ok(int dtype) { return dtype == BSMM_F32 || dtype == BSMM_F16 || dtype == BSMM_BF16; }
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
-inline unsigned capped(unsigned long long units) { return (unsigned)(units < (unsigned long long)EW_MAX_GRID ? units : EW_MAX_GRID); }
 
 // ---- the cuts -------------------------------------------------------------------------------------------------------------------------
 // axis 0 backward: a row of N in chunks of EW_SPAN columns
@@ -35,7 +31,7 @@ inline A1Cut a1_cut(int K, int N, int V) {
 }
 
 int check(const bsmm_ew_args* a) {
-    if (a == nullptr || a->K < 1 || a->N < 1 || (long long)a->K * (long long)a->N >= (1ll << 31)) return BSMM_ERR_ARG;
+    if (a == nullptr || a->K < 1 || a->N < 1 || !product_ok(a->K, a->N)) return BSMM_ERR_ARG;
     if ((a->axis != 0 && a->axis != 1) || !dtype_ok(a->dtype) || a->act < 0 || a->act > 2) return BSMM_ERR_ARG;
     return BSMM_OK;
 }
@@ -58,15 +54,9 @@ size_t grad_floats(const bsmm_ew_args* a) {
 int check_workspace(const bsmm_ew_args* a) {
     const size_t need = grad_floats(a) * sizeof(float);
     if (need == 0) return BSMM_OK;
-    if (a->workspace == nullptr || !aligned4(a->workspace) || a->workspace_bytes < need) return BSMM_ERR_ARG;
+    if (a->workspace == nullptr || !aligned_to(a->workspace, 4) || a->workspace_bytes < need) return BSMM_ERR_ARG;
     return BSMM_OK;
 }
-
-#define EW_LAUNCH(KERNEL, GRID, ...)                                   \
-    do {                                                               \
-        KERNEL<<<(GRID), 256, 0, st>>>(__VA_ARGS__);                   \
-        if (int rc_ = (int)hipGetLastError()) return rc_;              \
-    } while (0)
 
 template <class DT, bool VEC>
 int forward(const void* xv, const float* b, const void* rv, const uint64_t* state, uint32_t* mask, void* yv, int K, int N, int axis, int act, int drop,
@@ -74,7 +64,7 @@ int forward(const void* xv, const float* b, const void* rv, const uint64_t* stat
     typedef typename DT::T T;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const uint32_t total = (uint32_t)((long long)K * N), groups = 4u * ((total + 31u) / 32u);
-    EW_LAUNCH((ew_fwd_kernel<DT, VEC>), capped((groups + 255u) / 256u), static_cast<const T*>(xv), b, static_cast<const T*>(rv), state, mask,
+    BSMM_LAUNCH((ew_fwd_kernel<DT, VEC>), capped((groups + 255u) / 256u, EW_MAX_GRID), 256, st, static_cast<const T*>(xv), b, static_cast<const T*>(rv), state, mask,
               static_cast<T*>(yv), K, N, axis, act, drop, (uint32_t)threshold, scale, total, groups);
     return BSMM_OK;
 }
@@ -84,17 +74,9 @@ int forward_any(const void* x, const float* b, const void* res, const uint64_t* 
                 int drop, int threshold, float scale, void* stream) {
     bool vec = aligned16(x) && aligned16(y) && (res == nullptr || aligned16(res));
     if (b != nullptr) vec = vec && (axis == 0 ? N % 8 == 0 : K % 8 == 0 && aligned16(b));
-    switch (dtype) {
-        case BSMM_F32:
-            return vec ? forward<DTf32, true>(x, b, res, state, mask, y, K, N, axis, act, drop, threshold, scale, stream)
-                       : forward<DTf32, false>(x, b, res, state, mask, y, K, N, axis, act, drop, threshold, scale, stream);
-        case BSMM_F16:
-            return vec ? forward<DTf16, true>(x, b, res, state, mask, y, K, N, axis, act, drop, threshold, scale, stream)
-                       : forward<DTf16, false>(x, b, res, state, mask, y, K, N, axis, act, drop, threshold, scale, stream);
-        default:
-            return vec ? forward<DTbf16, true>(x, b, res, state, mask, y, K, N, axis, act, drop, threshold, scale, stream)
-                       : forward<DTbf16, false>(x, b, res, state, mask, y, K, N, axis, act, drop, threshold, scale, stream);
-    }
+    return with_dtype(dtype, vec, [&](auto dt, auto wide) {
+        return forward<decltype(dt), wide>(x, b, res, state, mask, y, K, N, axis, act, drop, threshold, scale, stream);
+    });
 }
 
 template <class DT, int V>
@@ -110,26 +92,22 @@ int backward(const void* dyv, const void* xyv, const float* b, const uint32_t* m
     if (a->axis == 0) {
         const int chunks = a0_chunks(N);
         const unsigned long long units = (unsigned long long)K * chunks;
-        EW_LAUNCH((ew_bwd_a0_kernel<DT, V>), capped(units), dy, xy, b, mask, dx, chunks > 1 ? ws : db, N, chunks, a->act, from_y, a->scale, (uint32_t)units);
-        if (chunks > 1) EW_LAUNCH(ew_sum_partials_kernel, sum_grid, ws, db, K, chunks, (size_t)1, (size_t)chunks);
+        BSMM_LAUNCH((ew_bwd_a0_kernel<DT, V>), capped(units, EW_MAX_GRID), 256, st, dy, xy, b, mask, dx, chunks > 1 ? ws : db, N, chunks, a->act, from_y, a->scale, (uint32_t)units);
+        if (chunks > 1) BSMM_LAUNCH(ew_sum_partials_kernel, sum_grid, 256, st, ws, db, K, chunks, (size_t)1, (size_t)chunks);
         return BSMM_OK;
     }
     const A1Cut c = a1_cut(K, N, V);
     const unsigned long long units = (unsigned long long)c.P * c.tiles;
-    EW_LAUNCH((ew_bwd_a1_kernel<DT, V>), capped(units), dy, xy, b, mask, dx, ws, K, N, c.KU, c.CT, c.RL, c.tiles, c.rpp, a->act, from_y, a->scale,
+    BSMM_LAUNCH((ew_bwd_a1_kernel<DT, V>), capped(units, EW_MAX_GRID), 256, st, dy, xy, b, mask, dx, ws, K, N, c.KU, c.CT, c.RL, c.tiles, c.rpp, a->act, from_y, a->scale,
               (uint32_t)units);
-    EW_LAUNCH(ew_sum_partials_kernel, sum_grid, ws, db, K, c.P, (size_t)K, (size_t)1);
+    BSMM_LAUNCH(ew_sum_partials_kernel, sum_grid, 256, st, ws, db, K, c.P, (size_t)K, (size_t)1);
     return BSMM_OK;
 }
 
 int backward_any(const void* dy, const void* xy, const float* b, const uint32_t* mask, void* dx, float* db, int from_y, const bsmm_ew_args* a) {
     bool vec = aligned16(dy) && (dx == nullptr || aligned16(dx)) && (a->act == 0 || aligned16(xy));
     vec = vec && (a->axis == 0 ? a->N % 8 == 0 : a->K % 8 == 0 && aligned16(b));
-    switch (a->dtype) {
-        case BSMM_F32: return vec ? backward<DTf32, 8>(dy, xy, b, mask, dx, db, from_y, a) : backward<DTf32, 1>(dy, xy, b, mask, dx, db, from_y, a);
-        case BSMM_F16: return vec ? backward<DTf16, 8>(dy, xy, b, mask, dx, db, from_y, a) : backward<DTf16, 1>(dy, xy, b, mask, dx, db, from_y, a);
-        default: return vec ? backward<DTbf16, 8>(dy, xy, b, mask, dx, db, from_y, a) : backward<DTbf16, 1>(dy, xy, b, mask, dx, db, from_y, a);
-    }
+    return with_dtype(a->dtype, vec, [&](auto dt, auto wide) { return backward<decltype(dt), (wide ? 8 : 1)>(dy, xy, b, mask, dx, db, from_y, a); });
 }
 
 }  // namespace
@@ -158,15 +136,15 @@ int bsmm_bias_act_grad(const void* dy, const void* x_or_y, const float* b, void*
 
 int bsmm_dropout_mask(uint32_t* mask, const uint64_t* state, int64_t n, int32_t threshold, void* stream) {
     if (mask == nullptr || state == nullptr || n < 1 || n >= ((int64_t)1 << 31) || threshold < 0 || threshold > 65536) return BSMM_ERR_ARG;
-    if (!aligned4(mask) || (reinterpret_cast<uintptr_t>(state) & 7)) return BSMM_ERR_ARG;
+    if (!aligned_to(mask, 4) || !aligned_to(state, 8)) return BSMM_ERR_ARG;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const uint32_t total = (uint32_t)n, words = (total + 31u) / 32u;
-    EW_LAUNCH(ew_mask_kernel, capped((words + 255u) / 256u), mask, state, (uint32_t)threshold, total, words);
+    BSMM_LAUNCH(ew_mask_kernel, capped((words + 255u) / 256u, EW_MAX_GRID), 256, st, mask, state, (uint32_t)threshold, total, words);
     return BSMM_OK;
 }
 
 int bsmm_dropout_apply(const void* x, const uint32_t* mask, void* y, int64_t n, float scale, int32_t dtype, void* stream) {
-    if (x == nullptr || mask == nullptr || y == nullptr || n < 1 || n >= ((int64_t)1 << 31) || !dtype_ok(dtype) || !aligned4(mask)) return BSMM_ERR_ARG;
+    if (x == nullptr || mask == nullptr || y == nullptr || n < 1 || n >= ((int64_t)1 << 31) || !dtype_ok(dtype) || !aligned_to(mask, 4)) return BSMM_ERR_ARG;
     return forward_any(x, nullptr, nullptr, nullptr, const_cast<uint32_t*>(mask), y, 1, (int)n, 0, dtype, BSMM_ACT_NONE, EW_DROP_READ, 0, scale, stream);
 }
 
@@ -175,15 +153,15 @@ int bsmm_bias_act_dropout(const void* x, const float* b, const void* residual, c
     if (int rc = check(args)) return rc;
     if (int rc = check_dropout(args)) return rc;
     if (x == nullptr || mask == nullptr || y == nullptr || (b == nullptr && args->act != BSMM_ACT_NONE)) return BSMM_ERR_ARG;
-    if (args->generate && (state == nullptr || (reinterpret_cast<uintptr_t>(state) & 7))) return BSMM_ERR_ARG;
-    if (!aligned4(mask)) return BSMM_ERR_ARG;
+    if (args->generate && (state == nullptr || !aligned_to(state, 8))) return BSMM_ERR_ARG;
+    if (!aligned_to(mask, 4)) return BSMM_ERR_ARG;
     return forward_any(x, b, residual, state, mask, y, args->K, args->N, args->axis, args->dtype, args->act,
                        args->generate ? EW_DROP_GENERATE : EW_DROP_READ, args->threshold, args->scale, args->stream);
 }
 
 int bsmm_bias_act_dropout_grad(const void* dy, const void* x, const float* b, const uint32_t* mask, void* dx, float* db, const bsmm_ew_args* args) {
     if (int rc = check(args)) return rc;
-    if (dy == nullptr || x == nullptr || b == nullptr || mask == nullptr || dx == nullptr || db == nullptr || !aligned4(mask)) return BSMM_ERR_ARG;
+    if (dy == nullptr || x == nullptr || b == nullptr || mask == nullptr || dx == nullptr || db == nullptr || !aligned_to(mask, 4)) return BSMM_ERR_ARG;
     if (int rc = check_workspace(args)) return rc;
     return backward_any(dy, x, b, mask, dx, db, 0, args);
 }

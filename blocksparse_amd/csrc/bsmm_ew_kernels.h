@@ -15,9 +15,10 @@
 //                           unit and every RL-th row of the partition (RL = 256 / column units when K is narrow), keeps V sums in registers,
 //                           lanes with the same columns meet in LDS in ascending order, one row of partials per partition.
 //   ew_sum_partials_kernel  db[k] = the partials in ascending order (sixteen slices per output, joined in LDS in a fixed order).
-// Units beyond the grid (at most EW_MAX_GRID workgroups) are taken by a grid stride.
+// Units beyond the grid (at most EW_MAX_GRID workgroups) are taken by a grid stride.  The 16-byte accesses and the wave sum are those of
+// bsmm_vec.h.
 #pragma once
-#include "bsmm_common.h"
+#include "bsmm_vec.h"
 
 // the multiply by the dropout scale and the add of the residual (and every sum) stay separate fp32 operations in this translation unit
 #pragma clang fp contract(off)
@@ -74,55 +75,6 @@ __device__ __forceinline__ float ew_act_grad(float g, float z, int act) {
     return g;
 }
 
-// ---- 8 consecutive elements <-> 8 floats by 16-byte accesses (p 16-byte aligned) ----
-template <class DT>
-__device__ __forceinline__ void ew_load8(const typename DT::T* p, float* v) {
-    if constexpr (!DT::is16) {
-        const float4 a = reinterpret_cast<const float4*>(p)[0], c = reinterpret_cast<const float4*>(p)[1];
-        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = c.x; v[5] = c.y; v[6] = c.z; v[7] = c.w;
-    } else {
-        const uint4 q = *reinterpret_cast<const uint4*>(p);
-        const uint32_t wd[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            v[2 * j] = DT::to_f32((uint16_t)(wd[j] & 0xffffu));
-            v[2 * j + 1] = DT::to_f32((uint16_t)(wd[j] >> 16));
-        }
-    }
-}
-
-template <class DT>
-__device__ __forceinline__ void ew_store8(typename DT::T* p, const float* v) {
-    if constexpr (!DT::is16) {
-        reinterpret_cast<float4*>(p)[0] = make_float4(v[0], v[1], v[2], v[3]);
-        reinterpret_cast<float4*>(p)[1] = make_float4(v[4], v[5], v[6], v[7]);
-    } else {
-        uint32_t wd[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) wd[j] = (uint32_t)DT::from_f32(v[2 * j]) | ((uint32_t)DT::from_f32(v[2 * j + 1]) << 16);
-        *reinterpret_cast<uint4*>(p) = make_uint4(wd[0], wd[1], wd[2], wd[3]);
-    }
-}
-
-// V elements at p: one group by 16-byte accesses, or one element
-template <class DT, int V>
-__device__ __forceinline__ void ew_load(const typename DT::T* p, float* v) {
-    if constexpr (V == 8) ew_load8<DT>(p, v);
-    else v[0] = DT::to_f32(p[0]);
-}
-
-template <class DT, int V>
-__device__ __forceinline__ void ew_store(typename DT::T* p, const float* v) {
-    if constexpr (V == 8) ew_store8<DT>(p, v);
-    else p[0] = DT::from_f32(v[0]);
-}
-
-__device__ __forceinline__ float ew_wave_sum(float v) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
 // =====================================================================================================================================
 // forward
 // =====================================================================================================================================
@@ -153,7 +105,7 @@ __global__ void __launch_bounds__(256) ew_fwd_kernel(const typename DT::T* __res
         const bool whole = VEC && live == 8;
         float v[8], bb[8], r[8], o[8];
         if (whole) {
-            ew_load8<DT>(x + i0, v);
+            vec_load<DT, 8>(x + i0, v);
         } else {
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[j] = j < live ? DT::to_f32(x[i0 + j]) : 0.f;
@@ -165,9 +117,7 @@ __global__ void __launch_bounds__(256) ew_fwd_kernel(const typename DT::T* __res
 #pragma unroll
                     for (int j = 0; j < 8; ++j) bb[j] = bk;
                 } else {
-                    const float4* bp = reinterpret_cast<const float4*>(b + i0 % (uint32_t)K);
-                    const float4 a = bp[0], d = bp[1];
-                    bb[0] = a.x; bb[1] = a.y; bb[2] = a.z; bb[3] = a.w; bb[4] = d.x; bb[5] = d.y; bb[6] = d.z; bb[7] = d.w;
+                    vec_load_f32<8>(b + i0 % (uint32_t)K, bb);
                 }
             } else if (axis == 0) {
                 uint32_t k = i0 / (uint32_t)N, pos = i0 - k * (uint32_t)N;
@@ -187,7 +137,7 @@ __global__ void __launch_bounds__(256) ew_fwd_kernel(const typename DT::T* __res
         }
         if (res != nullptr) {
             if (whole) {
-                ew_load8<DT>(res + i0, r);
+                vec_load<DT, 8>(res + i0, r);
             } else {
 #pragma unroll
                 for (int j = 0; j < 8; ++j) r[j] = j < live ? DT::to_f32(res[i0 + j]) : 0.f;
@@ -201,7 +151,7 @@ __global__ void __launch_bounds__(256) ew_fwd_kernel(const typename DT::T* __res
             o[j] = t;
         }
         if (whole) {
-            ew_store8<DT>(y + i0, o);
+            vec_store<DT, 8>(y + i0, o);
         } else {
 #pragma unroll
             for (int j = 0; j < 8; ++j)
@@ -232,8 +182,8 @@ template <class DT, int V>
 __device__ __forceinline__ void ew_bwd_unit(const typename DT::T* __restrict__ dy, const typename DT::T* __restrict__ xy, const uint32_t* __restrict__ mask,
                                             typename DT::T* __restrict__ dx, size_t i, const float* bb, int act, int from_y, float scale, float* acc) {
     float d[V], a[V], o[V];
-    ew_load<DT, V>(dy + i, d);
-    if (act != 0) ew_load<DT, V>(xy + i, a);
+    vec_load<DT, V>(dy + i, d);
+    if (act != 0) vec_load<DT, V>(xy + i, a);
     uint32_t keep = 0xffu;
     if (mask != nullptr) keep = V == 8 ? (uint32_t)reinterpret_cast<const uint8_t*>(mask)[i >> 3] : (mask[i >> 5] >> (i & 31)) & 1u;
 #pragma unroll
@@ -244,7 +194,7 @@ __device__ __forceinline__ void ew_bwd_unit(const typename DT::T* __restrict__ d
         o[j] = ew_act_grad(g, z, act);
         acc[j] += o[j];
     }
-    if (dx != nullptr) ew_store<DT, V>(dx + i, o);
+    if (dx != nullptr) vec_store<DT, V>(dx + i, o);
 }
 
 // grid: min(units, EW_MAX_GRID), units = K * chunks; unit u = (row k = u / chunks, chunk u % chunks) -> out[u]: db (chunks == 1) or the
@@ -269,7 +219,7 @@ __global__ void __launch_bounds__(256) ew_bwd_a0_kernel(const typename DT::T* __
         float s = acc[0];
 #pragma unroll
         for (int j = 1; j < V; ++j) s += acc[j];
-        s = ew_wave_sum(s);
+        s = wave_sum(s);
         __syncthreads();
         if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
         __syncthreads();
@@ -297,12 +247,8 @@ __global__ void __launch_bounds__(256) ew_bwd_a1_kernel(const typename DT::T* __
 #pragma unroll
         for (int j = 0; j < V; ++j) bb[j] = acc[j] = 0.f;
         if (mine) {
-            if constexpr (V == 8) {
-                const float4 a = reinterpret_cast<const float4*>(b + k0)[0], d = reinterpret_cast<const float4*>(b + k0)[1];
-                bb[0] = a.x; bb[1] = a.y; bb[2] = a.z; bb[3] = a.w; bb[4] = d.x; bb[5] = d.y; bb[6] = d.z; bb[7] = d.w;
-            } else {
-                bb[0] = b[k0];
-            }
+            if constexpr (V == 8) vec_load_f32<8>(b + k0, bb);
+            else bb[0] = b[k0];
 #pragma unroll 2
             for (long long r = r0 + rl; r < r1; r += RL) ew_bwd_unit<DT, V>(dy, xy, mask, dx, (size_t)r * (size_t)K + k0, bb, act, from_y, scale, acc);
         }

@@ -4,17 +4,15 @@
 #include <cstdint>
 
 #include "bsmm_lstm.h"
+#include "bsmm_host.h"
 #include "bsmm_lstm_kernels.h"
 
 using namespace bsmm;
 
 namespace {
 
-inline bool dtype_ok(int dtype) { return dtype == BSMM_F32 || dtype == BSMM_F16 || dtype == BSMM_BF16; }
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 int check(const bsmm_lstm_args* a, bool grad) {
-    if (a == nullptr || a->K < 1 || a->N < 1 || (long long)a->K * (long long)a->N >= (1ll << 31)) return BSMM_ERR_ARG;
+    if (a == nullptr || a->K < 1 || a->N < 1 || !product_ok(a->K, a->N)) return BSMM_ERR_ARG;
     if ((long long)a->K * 4 >= (1ll << 31)) return BSMM_ERR_ARG;
     if ((a->axis != 0 && a->axis != 1) || !dtype_ok(a->dtype)) return BSMM_ERR_ARG;
     if (a->axis == 1 && (a->gate_ld < a->K || (grad && a->dgate_ld < a->K))) return BSMM_ERR_ARG;
@@ -38,17 +36,12 @@ inline Geom geom(const bsmm_lstm_args* a) {
     return g;
 }
 
-inline unsigned grid_of(uint32_t units) {
-    const uint32_t wg = (units + 255u) / 256u;
-    return wg < (uint32_t)LSTM_MAX_GRID ? wg : (uint32_t)LSTM_MAX_GRID;
-}
+inline unsigned grid_of(uint32_t units) { return capped((units + 255u) / 256u, LSTM_MAX_GRID); }
 inline uint32_t magic_of(uint32_t upr) { return upr == 1u ? 0xffffffffu : (uint32_t)((1ull << 32) / upr); }
 
-#define LSTM_LAUNCH(KERNEL, GRID, ...)                                 \
-    do {                                                               \
-        KERNEL<<<(GRID), 256, 0, st>>>(__VA_ARGS__);                   \
-        if (int rc_ = (int)hipGetLastError()) return rc_;              \
-    } while (0)
+// elements of a 16-byte access
+template <class DT>
+constexpr int WIDE = DT::is16 ? 8 : 4;
 
 template <class DT, int V>
 int forward(const void* c, const void* i, const void* u, const void* f, const void* o, const float* bias, void* cn, void* hn, const Geom& g,
@@ -56,7 +49,7 @@ int forward(const void* c, const void* i, const void* u, const void* f, const vo
     typedef typename DT::T T;
     hipStream_t st = static_cast<hipStream_t>(a->stream);
     const uint32_t upr = g.cols / V, units = g.rows * upr;
-    LSTM_LAUNCH((lstm_fwd_kernel<DT, V>), grid_of(units), static_cast<const T*>(c), static_cast<const T*>(i), static_cast<const T*>(u),
+    BSMM_LAUNCH((lstm_fwd_kernel<DT, V>), grid_of(units), 256, st, static_cast<const T*>(c), static_cast<const T*>(i), static_cast<const T*>(u),
                 static_cast<const T*>(f), static_cast<const T*>(o), bias, static_cast<T*>(cn), static_cast<T*>(hn), g.cols, upr, magic_of(upr), units,
                 g.gate_ld, (uint32_t)a->K, g.by_row, a->forget_bias);
     return BSMM_OK;
@@ -68,7 +61,7 @@ int backward(const void* c, const void* i, const void* u, const void* f, const v
     typedef typename DT::T T;
     hipStream_t st = static_cast<hipStream_t>(a->stream);
     const uint32_t upr = g.cols / V, units = g.rows * upr;
-    LSTM_LAUNCH((lstm_bwd_kernel<DT, V>), grid_of(units), static_cast<const T*>(c), static_cast<const T*>(i), static_cast<const T*>(u),
+    BSMM_LAUNCH((lstm_bwd_kernel<DT, V>), grid_of(units), 256, st, static_cast<const T*>(c), static_cast<const T*>(i), static_cast<const T*>(u),
                 static_cast<const T*>(f), static_cast<const T*>(o), bias, static_cast<const T*>(eh), static_cast<const T*>(ec), static_cast<T*>(dc),
                 static_cast<T*>(di), static_cast<T*>(du), static_cast<T*>(df), static_cast<T*>(d_o), g.cols, upr, magic_of(upr), units, g.gate_ld,
                 g.dgate_ld, (uint32_t)a->K, g.by_row, a->forget_bias);
@@ -87,14 +80,9 @@ int bsmm_lstm_gates(const void* c, const void* i, const void* u, const void* f, 
     const uint32_t V = args->dtype == BSMM_F32 ? 4u : 8u;
     const bool wide = g.cols % V == 0 && g.gate_ld % V == 0 && aligned16(c) && aligned16(i) && aligned16(u) && aligned16(f) && aligned16(o) &&
                       aligned16(c_next) && aligned16(h_next);
-    switch (args->dtype) {
-        case BSMM_F32:
-            return wide ? forward<DTf32, 4>(c, i, u, f, o, bias, c_next, h_next, g, args) : forward<DTf32, 1>(c, i, u, f, o, bias, c_next, h_next, g, args);
-        case BSMM_F16:
-            return wide ? forward<DTf16, 8>(c, i, u, f, o, bias, c_next, h_next, g, args) : forward<DTf16, 1>(c, i, u, f, o, bias, c_next, h_next, g, args);
-        default:
-            return wide ? forward<DTbf16, 8>(c, i, u, f, o, bias, c_next, h_next, g, args) : forward<DTbf16, 1>(c, i, u, f, o, bias, c_next, h_next, g, args);
-    }
+    return with_dtype(args->dtype, wide, [&](auto dt, auto w) {
+        return forward<decltype(dt), (w ? WIDE<decltype(dt)> : 1)>(c, i, u, f, o, bias, c_next, h_next, g, args);
+    });
 }
 
 int bsmm_lstm_gates_grad(const void* c, const void* i, const void* u, const void* f, const void* o, const float* bias, const void* eh, const void* ec,
@@ -106,17 +94,9 @@ int bsmm_lstm_gates_grad(const void* c, const void* i, const void* u, const void
     const uint32_t V = args->dtype == BSMM_F32 ? 4u : 8u;
     const bool wide = g.cols % V == 0 && g.gate_ld % V == 0 && g.dgate_ld % V == 0 && aligned16(c) && aligned16(i) && aligned16(u) && aligned16(f) &&
                       aligned16(o) && aligned16(eh) && aligned16(ec) && aligned16(dc) && aligned16(di) && aligned16(du) && aligned16(df) && aligned16(d_o);
-    switch (args->dtype) {
-        case BSMM_F32:
-            return wide ? backward<DTf32, 4>(c, i, u, f, o, bias, eh, ec, dc, di, du, df, d_o, g, args)
-                        : backward<DTf32, 1>(c, i, u, f, o, bias, eh, ec, dc, di, du, df, d_o, g, args);
-        case BSMM_F16:
-            return wide ? backward<DTf16, 8>(c, i, u, f, o, bias, eh, ec, dc, di, du, df, d_o, g, args)
-                        : backward<DTf16, 1>(c, i, u, f, o, bias, eh, ec, dc, di, du, df, d_o, g, args);
-        default:
-            return wide ? backward<DTbf16, 8>(c, i, u, f, o, bias, eh, ec, dc, di, du, df, d_o, g, args)
-                        : backward<DTbf16, 1>(c, i, u, f, o, bias, eh, ec, dc, di, du, df, d_o, g, args);
-    }
+    return with_dtype(args->dtype, wide, [&](auto dt, auto w) {
+        return backward<decltype(dt), (w ? WIDE<decltype(dt)> : 1)>(c, i, u, f, o, bias, eh, ec, dc, di, du, df, d_o, g, args);
+    });
 }
 
 }  // extern "C"

@@ -6,16 +6,15 @@
 // Both layouts and both forms are ONE geometry: a matrix of `rows` x `cols` whose rows are contiguous in c (and c_next, h_next, eh, ec, dc)
 // and `gate_ld` (`dgate_ld`) elements apart in each of the four gate (d-gate) tensors -- axis 1: rows = N, cols = K, the bias goes by column;
 // axis 0: rows = K, cols = N, gate_ld = N, the bias goes by row.  The unit of work is V consecutive elements of a row: V = 8 (4 in fp32) by
-// 16-byte accesses when every pointer and every row start allows it, V = 1 otherwise.
+// 16-byte accesses when every pointer and every row start allows it, V = 1 otherwise (vec_load / vec_store of bsmm_vec.h; the stores pack a
+// pair of bf16 by one conversion, PACK2).
 //
 //   lstm_cell / lstm_cell_grad   the arithmetic, once: every kernel variant calls them, the order of operations is pinned, so the same values
 //                                give the same bits on every path.
 //   lstm_fwd_kernel<DT, V>       grid: min(ceil(units / 256), LSTM_MAX_GRID); a lane owns one unit, the rest by a grid stride.
 //   lstm_bwd_kernel<DT, V>       the same; eh or ec may be nullptr (zero).
 #pragma once
-#include <type_traits>
-
-#include "bsmm_common.h"
+#include "bsmm_vec.h"
 
 // no contraction the source does not spell out: a product and a sum fuse only where __fmaf_rn says so
 #pragma clang fp contract(off)
@@ -77,44 +76,6 @@ __device__ __forceinline__ LstmGrad lstm_cell_grad(const LstmCell& s, float c, f
     return g;
 }
 
-// ---- V consecutive elements <-> V floats: one 16-byte access (8 of a 16-bit type, 4 of fp32; p 16-byte aligned) or one element ----
-template <class DT, int V>
-__device__ __forceinline__ void lstm_load(const typename DT::T* p, float* v) {
-    if constexpr (V == 1) {
-        v[0] = DT::to_f32(p[0]);
-    } else if constexpr (!DT::is16) {
-        static_assert(V == 4, "fp32: 4 elements are 16 bytes");
-        const float4 a = *reinterpret_cast<const float4*>(p);
-        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-    } else {
-        static_assert(V == 8, "16-bit types: 8 elements are 16 bytes");
-        const uint4 q = *reinterpret_cast<const uint4*>(p);
-        const uint32_t wd[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            v[2 * j] = DT::to_f32((uint16_t)(wd[j] & 0xffffu));
-            v[2 * j + 1] = DT::to_f32((uint16_t)(wd[j] >> 16));
-        }
-    }
-}
-
-template <class DT, int V>
-__device__ __forceinline__ void lstm_store(typename DT::T* p, const float* v) {
-    if constexpr (V == 1) {
-        p[0] = DT::from_f32(v[0]);
-    } else if constexpr (!DT::is16) {
-        *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-        uint32_t wd[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if constexpr (std::is_same<DT, DTbf16>::value) wd[j] = bf16_pack2(v[2 * j], v[2 * j + 1]);      // (one conversion per pair, the same rounding)
-            else wd[j] = (uint32_t)DT::from_f32(v[2 * j]) | ((uint32_t)DT::from_f32(v[2 * j + 1]) << 16);
-        }
-        *reinterpret_cast<uint4*>(p) = make_uint4(wd[0], wd[1], wd[2], wd[3]);
-    }
-}
-
 // the bias values of V cells: gate g of cell k at bias[g * K + k]; by row: one cell, by column: cells col .. col + V - 1 (16-byte loads when
 // the bias allows it: on the wide path K and col are multiples of V).  No bias: zeros.
 template <int V>
@@ -131,11 +92,7 @@ __device__ __forceinline__ void lstm_bias(const float* __restrict__ bias, uint32
         } else {
             const float* p = bias + (size_t)g * K + col;
             if (V > 1 && (reinterpret_cast<uintptr_t>(bias) & 15) == 0) {
-#pragma unroll
-                for (int q = 0; q < V / 4; ++q) {
-                    const float4 a = reinterpret_cast<const float4*>(p)[q];
-                    bb[g][4 * q] = a.x; bb[g][4 * q + 1] = a.y; bb[g][4 * q + 2] = a.z; bb[g][4 * q + 3] = a.w;
-                }
+                vec_load_f32<V>(p, bb[g]);
             } else {
 #pragma unroll
                 for (int j = 0; j < V; ++j) bb[g][j] = p[j];
@@ -169,11 +126,11 @@ __global__ void __launch_bounds__(256) lstm_fwd_kernel(const typename DT::T* __r
         const uint32_t col = cu * (uint32_t)V;
         const size_t ci = (size_t)row * cols + col, gx = (size_t)row * gate_ld + col;
         float bb[4][V], vc[V], vi[V], vu[V], vf[V], vo[V], oc[V], oh[V];
-        lstm_load<DT, V>(c + ci, vc);
-        lstm_load<DT, V>(gi + gx, vi);
-        lstm_load<DT, V>(gu + gx, vu);
-        lstm_load<DT, V>(gf + gx, vf);
-        lstm_load<DT, V>(go + gx, vo);
+        vec_load<DT, V>(c + ci, vc);
+        vec_load<DT, V>(gi + gx, vi);
+        vec_load<DT, V>(gu + gx, vu);
+        vec_load<DT, V>(gf + gx, vf);
+        vec_load<DT, V>(go + gx, vo);
         lstm_bias<V>(bias, K, row, col, by_row, bb);
 #pragma unroll
         for (int j = 0; j < V; ++j) {
@@ -181,8 +138,8 @@ __global__ void __launch_bounds__(256) lstm_fwd_kernel(const typename DT::T* __r
             oc[j] = s.cn;
             oh[j] = s.h;
         }
-        lstm_store<DT, V>(cn + ci, oc);
-        lstm_store<DT, V>(hn + ci, oh);
+        vec_store<DT, V, true>(cn + ci, oc);
+        vec_store<DT, V, true>(hn + ci, oh);
     }
 }
 
@@ -202,19 +159,19 @@ __global__ void __launch_bounds__(256) lstm_bwd_kernel(const typename DT::T* __r
         const uint32_t col = cu * (uint32_t)V;
         const size_t ci = (size_t)row * cols + col, gx = (size_t)row * gate_ld + col, dx = (size_t)row * dgate_ld + col;
         float bb[4][V], vc[V], vi[V], vu[V], vf[V], vo[V], veh[V], vec[V];
-        lstm_load<DT, V>(c + ci, vc);
-        lstm_load<DT, V>(gi + gx, vi);
-        lstm_load<DT, V>(gu + gx, vu);
-        lstm_load<DT, V>(gf + gx, vf);
-        lstm_load<DT, V>(go + gx, vo);
+        vec_load<DT, V>(c + ci, vc);
+        vec_load<DT, V>(gi + gx, vi);
+        vec_load<DT, V>(gu + gx, vu);
+        vec_load<DT, V>(gf + gx, vf);
+        vec_load<DT, V>(go + gx, vo);
         if (eh != nullptr) {
-            lstm_load<DT, V>(eh + ci, veh);
+            vec_load<DT, V>(eh + ci, veh);
         } else {
 #pragma unroll
             for (int j = 0; j < V; ++j) veh[j] = 0.f;
         }
         if (ec != nullptr) {
-            lstm_load<DT, V>(ec + ci, vec);
+            vec_load<DT, V>(ec + ci, vec);
         } else {
 #pragma unroll
             for (int j = 0; j < V; ++j) vec[j] = 0.f;
@@ -231,11 +188,11 @@ __global__ void __launch_bounds__(256) lstm_bwd_kernel(const typename DT::T* __r
             odf[j] = g.df;
             odo[j] = g.d_o;
         }
-        lstm_store<DT, V>(dc + ci, odc);
-        lstm_store<DT, V>(di + dx, odi);
-        lstm_store<DT, V>(du + dx, odu);
-        lstm_store<DT, V>(df + dx, odf);
-        lstm_store<DT, V>(d_o + dx, odo);
+        vec_store<DT, V, true>(dc + ci, odc);
+        vec_store<DT, V, true>(di + dx, odi);
+        vec_store<DT, V, true>(du + dx, odu);
+        vec_store<DT, V, true>(df + dx, odf);
+        vec_store<DT, V, true>(d_o + dx, odo);
     }
 }
 

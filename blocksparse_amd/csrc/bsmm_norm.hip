@@ -3,14 +3,13 @@
 #include <cstdint>
 
 #include "bsmm_norm.h"
+#include "bsmm_host.h"
 #include "bsmm_norm_kernels.h"
 
 using namespace bsmm;
 
 namespace {
 
-inline bool dtype_ok(int dtype) { return dtype == BSMM_F32 || dtype == BSMM_F16 || dtype == BSMM_BF16; }
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline size_t round4(size_t n) { return (n + 3) & ~(size_t)3; }
 inline int vec_of(int dtype) { return dtype == BSMM_F32 ? 4 : 8; }
 
@@ -60,7 +59,7 @@ size_t workspace_floats(const bsmm_ln_args* a, int backward) {
 int check_workspace(const bsmm_ln_args* a, int backward) {
     const size_t need = workspace_floats(a, backward) * sizeof(float);
     if (need == 0) return BSMM_OK;
-    if (a->workspace == nullptr || (reinterpret_cast<uintptr_t>(a->workspace) & 3) || a->workspace_bytes < need) return BSMM_ERR_ARG;
+    if (a->workspace == nullptr || !aligned_to(a->workspace, 4) || a->workspace_bytes < need) return BSMM_ERR_ARG;
     return BSMM_OK;
 }
 
@@ -72,12 +71,6 @@ inline bool grids_ok(const bsmm_ln_args* a) {
     return (long long)c.strips * c.tiles * S <= lim && (long long)c.strips * c.split * S <= lim && S * N <= lim;
 }
 
-#define LN_LAUNCH(KERNEL, GRID, ...)                                   \
-    do {                                                               \
-        KERNEL<<<(GRID), 256, 0, st>>>(__VA_ARGS__);                   \
-        if (int rc_ = (int)hipGetLastError()) return rc_;              \
-    } while (0)
-
 template <class DT, bool VEC>
 int forward(const void* xv, const float* g, const float* b, void* yv, float* mean, float* rstd, const bsmm_ln_args* a) {
     typedef typename DT::T T;
@@ -87,16 +80,16 @@ int forward(const void* xv, const float* g, const float* b, void* yv, float* mea
     const int K = a->K, N = a->N, S = a->segments, Ks = K / S;
     if (a->axis == 1) {
         const long long R = (long long)N * S;
-        if (Ks <= LN_WAVE_LIMIT) LN_LAUNCH((ln_fwd_a1_kernel<DT, VEC, 64>), (unsigned)((R + 3) / 4), x, g, b, y, mean, rstd, N, S, Ks, a->relu, a->epsilon);
-        else if (Ks <= LN_ROW_LIMIT) LN_LAUNCH((ln_fwd_a1_kernel<DT, VEC, 256>), (unsigned)R, x, g, b, y, mean, rstd, N, S, Ks, a->relu, a->epsilon);
-        else LN_LAUNCH((ln_fwd_a1_long_kernel<DT, VEC>), (unsigned)R, x, g, b, y, mean, rstd, N, S, Ks, a->relu, a->epsilon);
+        if (Ks <= LN_WAVE_LIMIT) BSMM_LAUNCH((ln_fwd_a1_kernel<DT, VEC, 64>), (unsigned)((R + 3) / 4), 256, st, x, g, b, y, mean, rstd, N, S, Ks, a->relu, a->epsilon);
+        else if (Ks <= LN_ROW_LIMIT) BSMM_LAUNCH((ln_fwd_a1_kernel<DT, VEC, 256>), (unsigned)R, 256, st, x, g, b, y, mean, rstd, N, S, Ks, a->relu, a->epsilon);
+        else BSMM_LAUNCH((ln_fwd_a1_long_kernel<DT, VEC>), (unsigned)R, 256, st, x, g, b, y, mean, rstd, N, S, Ks, a->relu, a->epsilon);
         return BSMM_OK;
     }
     const A0Cut c = a0_cut(Ks, N, a->dtype);
     float* ws = static_cast<float*>(a->workspace);
-    LN_LAUNCH((ln_stats_a0_kernel<DT, VEC>), (unsigned)(c.strips * c.split * S), x, ws, N, S, Ks, c.strips, c.split, c.rps);
-    LN_LAUNCH((ln_stats_merge_a0_kernel<DT>), (unsigned)(((long long)S * N + 255) / 256), x, ws, mean, rstd, N, S, Ks, c.split, a->epsilon);
-    LN_LAUNCH((ln_norm_a0_kernel<DT, VEC>), (unsigned)(c.strips * c.tiles * S), x, g, b, mean, rstd, y, N, Ks, c.strips, c.tiles, a->relu);
+    BSMM_LAUNCH((ln_stats_a0_kernel<DT, VEC>), (unsigned)(c.strips * c.split * S), 256, st, x, ws, N, S, Ks, c.strips, c.split, c.rps);
+    BSMM_LAUNCH((ln_stats_merge_a0_kernel<DT>), (unsigned)(((long long)S * N + 255) / 256), 256, st, x, ws, mean, rstd, N, S, Ks, c.split, a->epsilon);
+    BSMM_LAUNCH((ln_norm_a0_kernel<DT, VEC>), (unsigned)(c.strips * c.tiles * S), 256, st, x, g, b, mean, rstd, y, N, Ks, c.strips, c.tiles, a->relu);
     return BSMM_OK;
 }
 
@@ -115,26 +108,26 @@ int backward(const void* dyv, const void* xv, const float* g, const float* b, co
         const int P = a1_groups(N);
         int rows = P;                                       // rows of partials
         if (Ks <= LN_WAVE_LIMIT) {
-            LN_LAUNCH((ln_bwd_a1_kernel<DT, VEC, 64>), (unsigned)(P * S), dy, x, g, b, mean, rstd, dx, ws, N, S, Ks, P, a->relu);
+            BSMM_LAUNCH((ln_bwd_a1_kernel<DT, VEC, 64>), (unsigned)(P * S), 256, st, dy, x, g, b, mean, rstd, dx, ws, N, S, Ks, P, a->relu);
             rows = 4 * P;
         } else if (Ks <= LN_ROW_LIMIT) {
-            LN_LAUNCH((ln_bwd_a1_kernel<DT, VEC, 256>), (unsigned)(P * S), dy, x, g, b, mean, rstd, dx, ws, N, S, Ks, P, a->relu);
+            BSMM_LAUNCH((ln_bwd_a1_kernel<DT, VEC, 256>), (unsigned)(P * S), 256, st, dy, x, g, b, mean, rstd, dx, ws, N, S, Ks, P, a->relu);
         } else {
-            LN_LAUNCH((ln_bwd_a1_long_kernel<DT, VEC>), (unsigned)((long long)N * S), dy, x, g, b, mean, rstd, dx, N, S, Ks, a->relu);
-            LN_LAUNCH((ln_dgdb_a1_kernel<DT>), dim3((unsigned)((K + 255) / 256), (unsigned)P), dy, x, g, b, mean, rstd, ws, N, K, Ks, P, a->relu);
+            BSMM_LAUNCH((ln_bwd_a1_long_kernel<DT, VEC>), (unsigned)((long long)N * S), 256, st, dy, x, g, b, mean, rstd, dx, N, S, Ks, a->relu);
+            BSMM_LAUNCH((ln_dgdb_a1_kernel<DT>), dim3((unsigned)((K + 255) / 256), (unsigned)P), 256, st, dy, x, g, b, mean, rstd, ws, N, K, Ks, P, a->relu);
         }
-        LN_LAUNCH(ln_sum_partials_kernel, sum_grid, ws, dg, db, K, rows);
+        BSMM_LAUNCH(ln_sum_partials_kernel, sum_grid, 256, st, ws, dg, db, K, rows);
         return BSMM_OK;
     }
     const A0Cut c = a0_cut(Ks, N, a->dtype);
     float* merged = ws + a0_slice_floats(Ks, N, S, a->dtype);
     float* part = merged + round4(2 * (size_t)S * N);
-    LN_LAUNCH((ln_bwd_sums_a0_kernel<DT, VEC>), (unsigned)(c.strips * c.split * S), dy, x, g, b, mean, rstd, ws, part, N, S, Ks, c.strips, c.split, c.rps,
+    BSMM_LAUNCH((ln_bwd_sums_a0_kernel<DT, VEC>), (unsigned)(c.strips * c.split * S), 256, st, dy, x, g, b, mean, rstd, ws, part, N, S, Ks, c.strips, c.split, c.rps,
               a->relu);
-    LN_LAUNCH(ln_sums_merge_a0_kernel, (unsigned)(((long long)S * N + 255) / 256), ws, merged, N, S, c.split);
-    LN_LAUNCH((ln_bwd_dx_a0_kernel<DT, VEC>), (unsigned)(c.strips * c.tiles * S), dy, x, g, b, mean, rstd, merged, dx, N, S, Ks, c.strips, c.tiles,
+    BSMM_LAUNCH(ln_sums_merge_a0_kernel, (unsigned)(((long long)S * N + 255) / 256), 256, st, ws, merged, N, S, c.split);
+    BSMM_LAUNCH((ln_bwd_dx_a0_kernel<DT, VEC>), (unsigned)(c.strips * c.tiles * S), 256, st, dy, x, g, b, mean, rstd, merged, dx, N, S, Ks, c.strips, c.tiles,
               a->relu);
-    LN_LAUNCH(ln_sum_partials_kernel, sum_grid, part, dg, db, K, c.strips);
+    BSMM_LAUNCH(ln_sum_partials_kernel, sum_grid, 256, st, part, dg, db, K, c.strips);
     return BSMM_OK;
 }
 
@@ -160,11 +153,7 @@ int bsmm_layer_norm(const void* x, const float* g, const float* b, void* y, floa
     if (!grids_ok(args)) return BSMM_ERR_UNSUPPORTED;
     bool vec = run_ok(args) && aligned16(x) && aligned16(y);
     vec = vec && (args->axis == 0 ? aligned16(mean) && aligned16(rstd) : aligned16(g) && aligned16(b));
-    switch (args->dtype) {
-        case BSMM_F32: return vec ? forward<DTf32, true>(x, g, b, y, mean, rstd, args) : forward<DTf32, false>(x, g, b, y, mean, rstd, args);
-        case BSMM_F16: return vec ? forward<DTf16, true>(x, g, b, y, mean, rstd, args) : forward<DTf16, false>(x, g, b, y, mean, rstd, args);
-        default: return vec ? forward<DTbf16, true>(x, g, b, y, mean, rstd, args) : forward<DTbf16, false>(x, g, b, y, mean, rstd, args);
-    }
+    return with_dtype(args->dtype, vec, [&](auto dt, auto wide) { return forward<decltype(dt), wide>(x, g, b, y, mean, rstd, args); });
 }
 
 int bsmm_layer_norm_grad(const void* dy, const void* x, const float* g, const float* b, const float* mean, const float* rstd, void* dx, float* dg,
@@ -177,15 +166,9 @@ int bsmm_layer_norm_grad(const void* dy, const void* x, const float* g, const fl
     if (!grids_ok(args)) return BSMM_ERR_UNSUPPORTED;
     bool vec = run_ok(args) && aligned16(dy) && aligned16(x) && aligned16(dx);
     vec = vec && (args->axis == 0 ? aligned16(mean) && aligned16(rstd) && aligned16(args->workspace) : aligned16(g) && aligned16(b));
-    switch (args->dtype) {
-        case BSMM_F32:
-            return vec ? backward<DTf32, true>(dy, x, g, b, mean, rstd, dx, dg, db, args) : backward<DTf32, false>(dy, x, g, b, mean, rstd, dx, dg, db, args);
-        case BSMM_F16:
-            return vec ? backward<DTf16, true>(dy, x, g, b, mean, rstd, dx, dg, db, args) : backward<DTf16, false>(dy, x, g, b, mean, rstd, dx, dg, db, args);
-        default:
-            return vec ? backward<DTbf16, true>(dy, x, g, b, mean, rstd, dx, dg, db, args)
-                       : backward<DTbf16, false>(dy, x, g, b, mean, rstd, dx, dg, db, args);
-    }
+    return with_dtype(args->dtype, vec, [&](auto dt, auto wide) {
+        return backward<decltype(dt), wide>(dy, x, g, b, mean, rstd, dx, dg, db, args);
+    });
 }
 
 }  // extern "C"

@@ -25,7 +25,7 @@
 //                           (partials per strip);  ln_sums_merge_a0_kernel;  ln_bwd_dx_a0_kernel writes dx.
 //   ln_sum_partials_kernel  dg / db = the partial rows added in ascending order (four slices per output, joined in LDS in a fixed order).
 #pragma once
-#include "bsmm_common.h"
+#include "bsmm_vec.h"
 
 namespace bsmm {
 
@@ -40,16 +40,10 @@ struct LnV {
     static constexpr int CH = LN_LANE_ELEMS / V;       // 16-byte chunks a lane holds
 };
 
-__device__ __forceinline__ float ln_wave_sum(float v) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
 // sum over the G lanes that share a row: a wave, or the four waves of the workgroup through `red` (every lane gets the same bits)
 template <int G>
 __device__ __forceinline__ float ln_group_sum(float v, float* red) {
-    v = ln_wave_sum(v);
+    v = wave_sum(v);
     if constexpr (G == 256) {
         __syncthreads();
         if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
@@ -59,24 +53,15 @@ __device__ __forceinline__ float ln_group_sum(float v, float* red) {
     return v;
 }
 
-// ---- V consecutive elements <-> V floats; VEC: one 16-byte access, all V valid; else element accesses, those at or beyond lim skipped ----
+// ---- V consecutive elements <-> V floats; VEC: one 16-byte access (bsmm_vec.h), all V valid; else element accesses, those at or beyond lim skipped ----
 template <class DT, bool VEC>
 __device__ __forceinline__ void ln_load(const typename DT::T* p, int lim, float* v) {
     constexpr int V = LnV<DT>::V;
     if constexpr (!VEC) {
 #pragma unroll
         for (int j = 0; j < V; ++j) v[j] = j < lim ? DT::to_f32(p[j]) : 0.f;
-    } else if constexpr (!DT::is16) {
-        const float4 a = *reinterpret_cast<const float4*>(p);
-        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
     } else {
-        const uint4 q = *reinterpret_cast<const uint4*>(p);
-        const uint32_t wd[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            v[2 * j] = DT::to_f32((uint16_t)(wd[j] & 0xffffu));
-            v[2 * j + 1] = DT::to_f32((uint16_t)(wd[j] >> 16));
-        }
+        vec_load<DT, V>(p, v);
     }
 }
 
@@ -87,13 +72,8 @@ __device__ __forceinline__ void ln_store(typename DT::T* p, int lim, const float
 #pragma unroll
         for (int j = 0; j < V; ++j)
             if (j < lim) p[j] = DT::from_f32(v[j]);
-    } else if constexpr (!DT::is16) {
-        *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
     } else {
-        uint32_t wd[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) wd[j] = (uint32_t)DT::from_f32(v[2 * j]) | ((uint32_t)DT::from_f32(v[2 * j + 1]) << 16);
-        *reinterpret_cast<uint4*>(p) = make_uint4(wd[0], wd[1], wd[2], wd[3]);
+        vec_store<DT, V>(p, v);
     }
 }
 
@@ -104,11 +84,7 @@ __device__ __forceinline__ void ln_load_f32(const float* p, int lim, float* v) {
 #pragma unroll
         for (int j = 0; j < NV; ++j) v[j] = j < lim ? p[j] : 0.f;
     } else {
-#pragma unroll
-        for (int q = 0; q < NV / 4; ++q) {
-            const float4 a = reinterpret_cast<const float4*>(p)[q];
-            v[4 * q] = a.x; v[4 * q + 1] = a.y; v[4 * q + 2] = a.z; v[4 * q + 3] = a.w;
-        }
+        vec_load_f32<NV>(p, v);
     }
 }
 
@@ -593,8 +569,8 @@ __global__ void __launch_bounds__(256) ln_bwd_sums_a0_kernel(const typename DT::
             s1[j] = fmaf(xhat, dg_, s1[j]);
             s2[j] += dg_;
         }
-        rdg = ln_wave_sum(rdg);
-        rdb = ln_wave_sum(rdb);
+        rdg = wave_sum(rdg);
+        rdb = wave_sum(rdb);
         if (lane == 0) {
             part[((size_t)strip * 2) * K + f] = rdg;
             part[((size_t)strip * 2 + 1) * K + f] = rdb;

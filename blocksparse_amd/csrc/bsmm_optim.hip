@@ -1,18 +1,14 @@
 // bsmm_optim.hip -- C-ABI entry points of include/bsmm_optim.h: argument checks, then launches of the kernels in bsmm_optim_kernels.h.
 // No allocation, no host sync, no environment, no state.
 #include <cstdint>
-#include <type_traits>
 
+#include "bsmm_host.h"
 #include "bsmm_optim.h"
 #include "bsmm_optim_kernels.h"
 
 using namespace bsmm;
 
 namespace {
-
-inline bool bsize_ok(int bsize) { return bsize == 8 || bsize == 16 || bsize == 32 || bsize == 64; }
-inline bool dtype_ok(int dtype) { return dtype == BSMM_F32 || dtype == BSMM_F16 || dtype == BSMM_BF16; }
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // workgroups for `work` lane-steps: one step per lane up to the cap, strided beyond it
 inline unsigned grid_for(size_t work, int cap) {
@@ -75,7 +71,7 @@ int launch_sum_squared(const void* x, float* slots, size_t size, float grad_scal
 }
 
 inline bool workspace_ok(const void* workspace, size_t bytes, int tensor_cnt) {
-    return workspace != nullptr && (reinterpret_cast<uintptr_t>(workspace) & 3) == 0 && bytes >= bsmm_sum_squared_workspace_bytes(tensor_cnt);
+    return workspace != nullptr && aligned_to(workspace, 4) && bytes >= bsmm_sum_squared_workspace_bytes(tensor_cnt);
 }
 
 }  // namespace
@@ -98,11 +94,7 @@ int bsmm_adam(const bsmm_adam_args* a) {
     p.saturate = a->saturate;
     p.zero_infs = a->zero_infs != 0;
     p.zero_nans = a->zero_nans != 0;
-    switch (a->grad_dtype) {
-        case BSMM_F32: return adam_p16<DTf32>(a, p);
-        case BSMM_F16: return adam_p16<DTf16>(a, p);
-        default: return adam_p16<DTbf16>(a, p);
-    }
+    return with_dtype(a->grad_dtype, [&](auto dt) { return adam_p16<decltype(dt)>(a, p); });
 }
 
 int bsmm_ema(void* ema, const float* param, const float* gate, float decay, size_t size, int32_t bsize, int32_t ema_dtype, void* stream) {
@@ -110,11 +102,7 @@ int bsmm_ema(void* ema, const float* param, const float* gate, float decay, size
     if (int rc = check_shape(size, bsize, gate, nullptr)) return rc;
     if (!dtype_ok(ema_dtype)) return BSMM_ERR_UNSUPPORTED;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (ema_dtype) {
-        case BSMM_F32: return launch_ema<DTf32>(ema, param, gate, decay, size, bsize, st);
-        case BSMM_F16: return launch_ema<DTf16>(ema, param, gate, decay, size, bsize, st);
-        default: return launch_ema<DTbf16>(ema, param, gate, decay, size, bsize, st);
-    }
+    return with_dtype(ema_dtype, [&](auto dt) { return launch_ema<decltype(dt)>(ema, param, gate, decay, size, bsize, st); });
 }
 
 size_t bsmm_sum_squared_workspace_bytes(int32_t tensor_cnt) {
@@ -128,11 +116,9 @@ int bsmm_sum_squared(const void* x, size_t size, int32_t dtype, float grad_scale
     if (!workspace_ok(workspace, workspace_bytes, tensor_cnt)) return BSMM_ERR_WORKSPACE;
     float* slots = static_cast<float*>(workspace) + (size_t)tensor_idx * OPT_SS_SLOTS;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (dtype) {
-        case BSMM_F32: return launch_sum_squared<DTf32>(x, slots, size, grad_scale, saturate, zero_infs != 0, zero_nans != 0, st);
-        case BSMM_F16: return launch_sum_squared<DTf16>(x, slots, size, grad_scale, saturate, zero_infs != 0, zero_nans != 0, st);
-        default: return launch_sum_squared<DTbf16>(x, slots, size, grad_scale, saturate, zero_infs != 0, zero_nans != 0, st);
-    }
+    return with_dtype(dtype, [&](auto dt) {
+        return launch_sum_squared<decltype(dt)>(x, slots, size, grad_scale, saturate, zero_infs != 0, zero_nans != 0, st);
+    });
 }
 
 int bsmm_clip_norm(const void* workspace, size_t workspace_bytes, int32_t tensor_cnt, float clip_norm, float* norm_out, float* scale_out,

@@ -2,8 +2,8 @@
 // the kernels in bsmm_optim_list_kernels.h.  No allocation, no copies, no host sync, no environment, no state.
 #include <cstdint>
 #include <cstring>
-#include <type_traits>
 
+#include "bsmm_host.h"
 #include "bsmm_optim_list.h"
 #include "bsmm_optim_list_kernels.h"
 
@@ -15,10 +15,6 @@ constexpr int32_t LIST_MAX_ROWS = 1 << 20;               // the limit of bsmm_cl
 
 // the checks and the grid rule of bsmm_optim.hip (file-local there), restated so that a row is accepted here exactly when the per-tensor
 // calls accept it and gets the workgroups their launches would use (the Adam stage: up to OPT_LIST_ADAM_GRID, see there)
-inline bool bsize_ok(int bsize) { return bsize == 8 || bsize == 16 || bsize == 32 || bsize == 64; }
-inline bool dtype_ok(int dtype) { return dtype == BSMM_F32 || dtype == BSMM_F16 || dtype == BSMM_BF16; }
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 inline unsigned grid_for(size_t work, int cap) {
     const size_t g = (work + OPT_THREADS - 1) / OPT_THREADS;
     return (unsigned)(g < 1 ? 1 : (g > (size_t)cap ? (size_t)cap : g));
@@ -123,7 +119,7 @@ int bsmm_opt_list_build(const bsmm_opt_tensor* rows, int32_t count, void* table_
 
 int bsmm_opt_advance(bsmm_opt_state* state, const float* lr, const float* lr_new, double beta1, double beta2, int32_t zero_init_variables,
                      void* stream) {
-    if (state == nullptr || lr == nullptr || (reinterpret_cast<uintptr_t>(state) & 3) != 0) return BSMM_ERR_ARG;
+    if (state == nullptr || lr == nullptr || !aligned_to(state, 4)) return BSMM_ERR_ARG;
     opt_advance_kernel<<<1, 64, 0, reinterpret_cast<hipStream_t>(stream)>>>(reinterpret_cast<OptState*>(state), lr, lr_new, beta1, beta2,
                                                                              zero_init_variables != 0);
     return (int)hipGetLastError();
@@ -159,7 +155,7 @@ int bsmm_ema_list(const bsmm_opt_list* info, const void* table_dev, float decay,
 int bsmm_sum_squared_list(const bsmm_opt_list* info, const void* table_dev, float grad_scale, float saturate, int32_t zero_infs,
                           int32_t zero_nans, void* workspace, size_t workspace_bytes, void* stream) {
     if (!list_ok(info, table_dev)) return BSMM_ERR_ARG;
-    if (workspace == nullptr || (reinterpret_cast<uintptr_t>(workspace) & 3) != 0 || workspace_bytes < bsmm_sum_squared_workspace_bytes(info->count))
+    if (workspace == nullptr || !aligned_to(workspace, 4) || workspace_bytes < bsmm_sum_squared_workspace_bytes(info->count))
         return BSMM_ERR_WORKSPACE;
     opt_sum_squared_list_kernel<<<(unsigned)info->sum_squared_grid, OPT_THREADS, 0, reinterpret_cast<hipStream_t>(stream)>>>(
         table_rows(table_dev), table_prefix(table_dev, info->count, 2), info->count, reinterpret_cast<float*>(workspace), grad_scale, saturate,

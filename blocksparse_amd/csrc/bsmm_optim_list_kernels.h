@@ -65,55 +65,7 @@ __device__ __forceinline__ int opt_find_row(const int* __restrict__ prefix, int 
     return lo;
 }
 
-// ---- Adam: the loop of opt_adam_kernel for workgroup w of G -----------------------------------------------------------------------------
-template <class GT, class PT, bool VEC>
-__device__ __forceinline__ void opt_adam_row(float* __restrict__ param, float* __restrict__ mean, float* __restrict__ var,
-                                             const typename GT::T* __restrict__ grad, void* __restrict__ param16, const float* __restrict__ gate,
-                                             const float* __restrict__ lr_select, size_t size, int bb, const AdamParams& a, float gs, size_t w, size_t G) {
-    const bool per_block = gate != nullptr || lr_select != nullptr;
-    const size_t tid = w * OPT_THREADS + threadIdx.x, nthreads = G * OPT_THREADS;
-    size_t done = 0;
-    if constexpr (VEC) {
-        const size_t units = size >> 2;
-        done = units << 2;
-        const bool uniform = bb >= 256;
-        for (size_t u = tid; u < units; u += nthreads) {
-            const size_t i = u << 2;
-            float lr = a.lr;
-            if (per_block) {
-                const int b = opt_block_of(i, bb, uniform);
-                if (gate != nullptr && gate[b] == 0.f) continue;
-                if (lr_select != nullptr && lr_select[b] != 0.f) lr = a.lr_new;
-            }
-            float g[4], m[4], v[4], p[4];
-            opt_load4<GT>(grad + i, g);
-            opt_load4<DTf32>(mean + i, m);
-            opt_load4<DTf32>(var + i, v);
-            opt_load4<DTf32>(param + i, p);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) adam_elem(g[j], m[j], v[j], p[j], a, gs, lr);
-            opt_store4<DTf32>(mean + i, m);
-            opt_store4<DTf32>(var + i, v);
-            opt_store4<DTf32>(param + i, p);
-            if constexpr (!std::is_same<PT, NoP16>::value) opt_store4<PT>(reinterpret_cast<typename PT::T*>(param16) + i, p);
-        }
-    }
-    for (size_t i = done + tid; i < size; i += nthreads) {
-        float lr = a.lr;
-        if (per_block) {
-            const int b = opt_block_of(i, bb, false);
-            if (gate != nullptr && gate[b] == 0.f) continue;
-            if (lr_select != nullptr && lr_select[b] != 0.f) lr = a.lr_new;
-        }
-        float m = mean[i], v = var[i], p = param[i];
-        adam_elem(GT::to_f32(grad[i]), m, v, p, a, gs, lr);
-        mean[i] = m;
-        var[i] = v;
-        param[i] = p;
-        if constexpr (!std::is_same<PT, NoP16>::value) reinterpret_cast<typename PT::T*>(param16)[i] = PT::from_f32(p);
-    }
-}
-
+// ---- Adam: opt_adam_row for workgroup w of the G of its row -------------------------------------------------------------------------------
 template <class GT, class PT>
 __device__ __forceinline__ void opt_adam_path(const OptRow& r, const AdamParams& a, float gs, size_t w, size_t G) {
     const typename GT::T* grad = reinterpret_cast<const typename GT::T*>(r.grad);
@@ -150,33 +102,7 @@ __global__ void __launch_bounds__(OPT_THREADS) opt_adam_list_kernel(const OptRow
     }
 }
 
-// ---- moving average: the loop of opt_ema_kernel for workgroup w of G ---------------------------------------------------------------------
-template <class ET, bool VEC>
-__device__ __forceinline__ void opt_ema_row(typename ET::T* __restrict__ ema, const float* __restrict__ param, const float* __restrict__ gate,
-                                            size_t size, int bb, float rate, size_t w, size_t G) {
-    const size_t tid = w * OPT_THREADS + threadIdx.x, nthreads = G * OPT_THREADS;
-    size_t done = 0;
-    if constexpr (VEC) {
-        const size_t units = size >> 2;
-        done = units << 2;
-        const bool uniform = bb >= 256;
-        for (size_t u = tid; u < units; u += nthreads) {
-            const size_t i = u << 2;
-            if (gate != nullptr && gate[opt_block_of(i, bb, uniform)] == 0.f) continue;
-            float e[4], p[4];
-            opt_load4<ET>(ema + i, e);
-            opt_load4<DTf32>(param + i, p);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) e[j] = ema_elem(e[j], p[j], rate);
-            opt_store4<ET>(ema + i, e);
-        }
-    }
-    for (size_t i = done + tid; i < size; i += nthreads) {
-        if (gate != nullptr && gate[opt_block_of(i, bb, false)] == 0.f) continue;
-        ema[i] = ET::from_f32(ema_elem(ET::to_f32(ema[i]), param[i], rate));
-    }
-}
-
+// ---- moving average ------------------------------------------------------------------------------------------------------------------------
 template <class ET>
 __device__ __forceinline__ void opt_ema_path(const OptRow& r, float rate, size_t w, size_t G) {
     typename ET::T* ema = reinterpret_cast<typename ET::T*>(r.ema);
@@ -196,44 +122,7 @@ __global__ void __launch_bounds__(OPT_THREADS) opt_ema_list_kernel(const OptRow*
     }
 }
 
-// ---- global norm, stage 1: the body of opt_sum_squared_kernel for workgroup w of G --------------------------------------------------------
-template <class DT, bool VEC>
-__device__ __forceinline__ void opt_sum_squared_row(const typename DT::T* __restrict__ x, float* __restrict__ slots, size_t size, float grad_scale,
-                                                    float saturate, int zero_infs, int zero_nans, size_t w, size_t G, float* share) {
-    constexpr int W = VEC ? (DT::is16 ? 8 : 4) : 1;
-    const size_t tid = w * OPT_THREADS + threadIdx.x, nthreads = G * OPT_THREADS;
-    const size_t units = size / W;
-    float acc = 0.f;
-    for (size_t u = tid; u < units; u += nthreads) {
-        float v[W];
-        if constexpr (!VEC) {
-            v[0] = DT::to_f32(x[u]);
-        } else if constexpr (!DT::is16) {
-            opt_load4<DT>(x + u * 4, v);
-        } else {
-            const uint4 q = *reinterpret_cast<const uint4*>(x + u * 8);
-            const uint32_t wd[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                v[2 * j] = DT::to_f32((uint16_t)(wd[j] & 0xffffu));
-                v[2 * j + 1] = DT::to_f32((uint16_t)(wd[j] >> 16));
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < W; ++j) {
-            const float s = opt_pre(v[j], zero_infs, zero_nans, saturate) * grad_scale;
-            acc = fmaf(s, s, acc);
-        }
-    }
-    if (W > 1 && tid < size - units * W) {                   // the size % W trailing elements, one each in the first lanes of the row's grid
-        const float s = opt_pre(DT::to_f32(x[units * W + tid]), zero_infs, zero_nans, saturate) * grad_scale;
-        acc = fmaf(s, s, acc);
-    }
-    const float total = opt_group_sum(acc, share);
-    if (threadIdx.x == 0) slots[w] = total;
-    for (size_t s = G + tid; s < (size_t)OPT_SS_SLOTS; s += nthreads) slots[s] = 0.f;
-}
-
+// ---- global norm, stage 1 ------------------------------------------------------------------------------------------------------------------
 template <class DT>
 __device__ __forceinline__ void opt_sum_squared_path(const OptRow& r, float* slots, float grad_scale, float saturate, int zero_infs, int zero_nans,
                                                      size_t w, size_t G, float* share) {

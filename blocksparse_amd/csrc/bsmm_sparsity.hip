@@ -2,16 +2,13 @@
 // bsmm_sparsity_kernels.h.  No allocation, no host sync, no environment, no state.
 #include <cstdint>
 
+#include "bsmm_host.h"
 #include "bsmm_sparsity.h"
 #include "bsmm_sparsity_kernels.h"
 
 using namespace bsmm;
 
 namespace {
-
-inline bool bsize_ok(int bsize) { return bsize == 8 || bsize == 16 || bsize == 32 || bsize == 64; }
-inline bool dtype_ok(int dtype) { return dtype == BSMM_F32 || dtype == BSMM_F16 || dtype == BSMM_BF16; }
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // how bsmm_reduced_dw cuts the contraction: slices of at least 128 (a multiple of 64) terms, at most ~2048 waves in all.  `S_bound` (what
 // the workspace is sized for) is non-decreasing in Kc; the launch uses S <= S_bound slices, none of them empty.
@@ -46,11 +43,7 @@ int norm_dispatch(const void* w, float* out, int blocks, int bsize, int dtype, i
     if (out == nullptr) return BSMM_ERR_ARG;
     if (norm_type != BSMM_NORM_MAX && norm_type != BSMM_NORM_L2) return BSMM_ERR_UNSUPPORTED;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (dtype) {
-        case BSMM_F32: return launch_norm<DTf32>(w, out, blocks, bsize, norm_type, as_gate, threshold, st);
-        case BSMM_F16: return launch_norm<DTf16>(w, out, blocks, bsize, norm_type, as_gate, threshold, st);
-        default: return launch_norm<DTbf16>(w, out, blocks, bsize, norm_type, as_gate, threshold, st);
-    }
+    return with_dtype(dtype, [&](auto dt) { return launch_norm<decltype(dt)>(w, out, blocks, bsize, norm_type, as_gate, threshold, st); });
 }
 
 template <class DT>
@@ -104,11 +97,7 @@ int bsmm_block_threshold_prune(const void* w, float* gate, float threshold, int3
 int bsmm_block_l2_decay(void* w, const float* gate, float rate, float epsilon, int32_t blocks, int32_t bsize, int32_t dtype, void* stream) {
     if (int rc = check_blocks(w, blocks, bsize, dtype)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (dtype) {
-        case BSMM_F32: return launch_decay<DTf32>(w, gate, rate, epsilon, blocks, bsize, st);
-        case BSMM_F16: return launch_decay<DTf16>(w, gate, rate, epsilon, blocks, bsize, st);
-        default: return launch_decay<DTbf16>(w, gate, rate, epsilon, blocks, bsize, st);
-    }
+    return with_dtype(dtype, [&](auto dt) { return launch_decay<decltype(dt)>(w, gate, rate, epsilon, blocks, bsize, st); });
 }
 
 int bsmm_block_prune(float* gate, const int32_t* idx, int32_t blocks, int32_t keep, void* stream) {
@@ -132,11 +121,10 @@ int bsmm_feature_reduce(const void* const* xs, int32_t pcount, void* out, int32_
         if (p < pcount && !aligned16(xs[p])) in_aligned = false;
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (dtype) {
-        case BSMM_F32: return launch_reduce<DTf32, DTbf16>(list, out, pcount, F, N, bsize, axis, norm_type, in_aligned, st);
-        case BSMM_F16: return launch_reduce<DTf16, DTf16>(list, out, pcount, F, N, bsize, axis, norm_type, in_aligned, st);
-        default: return launch_reduce<DTbf16, DTbf16>(list, out, pcount, F, N, bsize, axis, norm_type, in_aligned, st);
-    }
+    return with_dtype(dtype, [&](auto dt) {                  // (fp32 activations reduce to bf16)
+        typedef decltype(dt) DT;
+        return launch_reduce<DT, std::conditional_t<DT::is16, DT, DTbf16>>(list, out, pcount, F, N, bsize, axis, norm_type, in_aligned, st);
+    });
 }
 
 size_t bsmm_reduced_dw_workspace_bytes(int32_t CB, int32_t KB, int32_t contraction) {
@@ -150,7 +138,7 @@ int bsmm_reduced_dw(const void* x_red, const void* y_red, float* dw, int32_t CB,
     if (x_red == nullptr || y_red == nullptr || dw == nullptr || CB <= 0 || KB <= 0 || contraction <= 0) return BSMM_ERR_ARG;
     if (red_dtype != BSMM_F16 && red_dtype != BSMM_BF16) return BSMM_ERR_UNSUPPORTED;
     if ((long long)((CB + 31) / 32) * ((KB + 31) / 32) > (1 << 20)) return BSMM_ERR_UNSUPPORTED;
-    if (workspace == nullptr || (reinterpret_cast<uintptr_t>(workspace) & 3) || workspace_bytes < bsmm_reduced_dw_workspace_bytes(CB, KB, contraction))
+    if (workspace == nullptr || !aligned_to(workspace, 4) || workspace_bytes < bsmm_reduced_dw_workspace_bytes(CB, KB, contraction))
         return BSMM_ERR_WORKSPACE;
     if (scale == 0.f) return BSMM_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);

@@ -13,20 +13,9 @@
 //            bsmm_common.h): in a step of 64, lane half h holds k = 32 h + 8 q + j in fragment q -- 64 contiguous bytes per lane.
 //            sp_rdw_sum_kernel adds the slices in ascending order and applies scale / accumulate.
 #pragma once
-#include "bsmm_common.h"
+#include "bsmm_vec.h"
 
 namespace bsmm {
-
-__device__ __forceinline__ float sp_wave_sum(float v) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-__device__ __forceinline__ float sp_wave_max(float v) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
-    return v;
-}
 
 // ---- weights: one wave per block, four blocks per workgroup ------------------------------------------------------------------
 // norm_type 0: max |w|, 1: sqrt(sum w^2).  as_gate: out[b] = norm < threshold ? 0 : 1 (blocksparse_threshold_prune), else out[b] = norm.
@@ -40,14 +29,14 @@ __global__ void __launch_bounds__(256) sp_block_norm_kernel(const typename DT::T
     if (norm_type == 0) {
 #pragma unroll 4
         for (int i = lane; i < bb; i += 64) acc = fmaxf(acc, fabsf(DT::to_f32(p[i])));
-        acc = sp_wave_max(acc);
+        acc = wave_max(acc);
     } else {
 #pragma unroll 4
         for (int i = lane; i < bb; i += 64) {
             const float v = DT::to_f32(p[i]);
             acc = fmaf(v, v, acc);
         }
-        acc = sqrtf(sp_wave_sum(acc));
+        acc = sqrtf(wave_sum(acc));
     }
     if (lane == 0) out[b] = as_gate ? (acc < threshold ? 0.f : 1.f) : acc;
 }
@@ -66,7 +55,7 @@ __global__ void __launch_bounds__(256) sp_block_l2_decay_kernel(typename DT::T* 
         const float v = DT::to_f32(p[i]);
         acc = fmaf(v, v, acc);
     }
-    const float decay = fminf(rate / sqrtf(sp_wave_sum(acc) + epsilon), 1.f);
+    const float decay = fminf(rate / sqrtf(wave_sum(acc) + epsilon), 1.f);
 #pragma unroll 4
     for (int i = lane; i < bb; i += 64) {
         const float v = DT::to_f32(p[i]);
@@ -82,32 +71,15 @@ __global__ void __launch_bounds__(256) sp_block_prune_kernel(float* __restrict__
     if (b < (uint32_t)blocks) gate[b] = i < keep ? 1.f : 0.f;
 }
 
-// ---- 8 consecutive elements <-> 8 floats -------------------------------------------------------------------------------------
+// ---- 8 consecutive elements -> 8 floats: 16-byte accesses (bsmm_vec.h) or, for a pointer that is not aligned, elements ---------------
 template <class DT, bool ALIGNED>
 __device__ __forceinline__ void sp_load8(const typename DT::T* p, float v[8]) {
     if constexpr (!ALIGNED) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = DT::to_f32(p[j]);
-    } else if constexpr (!DT::is16) {
-        const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
-        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
     } else {
-        const uint4 q = *reinterpret_cast<const uint4*>(p);
-        const uint32_t wd[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            v[2 * j] = DT::to_f32((uint16_t)(wd[j] & 0xffffu));
-            v[2 * j + 1] = DT::to_f32((uint16_t)(wd[j] >> 16));
-        }
+        vec_load<DT, 8>(p, v);
     }
-}
-
-template <class OT>
-__device__ __forceinline__ uint4 sp_pack8(const float v[8]) {
-    uint32_t wd[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) wd[j] = (uint32_t)OT::from_f32(v[2 * j]) | ((uint32_t)OT::from_f32(v[2 * j + 1]) << 16);
-    return make_uint4(wd[0], wd[1], wd[2], wd[3]);
 }
 
 // acc <- max(acc, |v|) or acc + v^2
@@ -135,7 +107,7 @@ __global__ void __launch_bounds__(256) sp_reduce_a0_kernel(PtrList8 xs, uint16_t
     }
     uint16_t* dst = out + ((size_t)fb * pcount + p) * N + n;
     if constexpr (ALIGNED) {
-        *reinterpret_cast<uint4*>(dst) = sp_pack8<OT>(acc);
+        vec_store<OT, 8>(dst, acc);
     } else {
 #pragma unroll
         for (int j = 0; j < 8; ++j) dst[j] = OT::from_f32(acc[j]);
@@ -195,7 +167,7 @@ __global__ void __launch_bounds__(256) sp_reduce_a1_kernel(PtrList8 xs, uint16_t
         }
         uint16_t* dst = out + ((size_t)fb * pcount + p) * N + n;
         if (vec_out) {                                   // (N % 8 == 0: the 8 columns are all inside)
-            *reinterpret_cast<uint4*>(dst) = sp_pack8<OT>(v);
+            vec_store<OT, 8>(dst, v);
         } else {
 #pragma unroll
             for (int j = 0; j < 8; ++j)

@@ -27,10 +27,6 @@ except Exception:  # pragma: no cover
     torch = None
 
 
-def _codes():
-    return {torch.float32: _lib.F32, torch.float16: _lib.F16, torch.bfloat16: _lib.BF16}
-
-
 def _idx32(idx, device):
     if torch is None:
         raise RuntimeError("blocksparse_amd needs PyTorch-ROCm for device memory")
@@ -50,9 +46,10 @@ def _table(t, what):
         raise RuntimeError("blocksparse_amd needs PyTorch-ROCm for device memory")
     if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
         raise RuntimeError("blocksparse_amd: %s must be a tensor on a ROCm device (no CPU fallback)" % what)
-    if t.dtype not in _codes():
+    code = _lib.dtype_code(t.dtype)
+    if code is None:
         raise ValueError("embedding_lookup: %s must be float32, float16 or bfloat16, got %s" % (what, t.dtype))
-    return _codes()[t.dtype]
+    return code
 
 
 def sort_order(idx):

@@ -56,12 +56,12 @@ def _dtype_code(x, what):
         raise RuntimeError("blocksparse_amd needs PyTorch-ROCm for device memory")
     if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
         raise RuntimeError("blocksparse_amd: %s must be a tensor on a ROCm device (no CPU fallback)" % what)
-    codes = {torch.float32: _lib.F32, torch.float16: _lib.F16, torch.bfloat16: _lib.BF16}
-    if x.dtype not in codes:
+    code = _lib.dtype_code(x.dtype)
+    if code is None:
         raise ValueError("ewops: %s must be float32, float16 or bfloat16, got %s" % (what, x.dtype))
     if x.numel() == 0 or x.numel() >= 2 ** 31:
         raise ValueError("ewops: %s must have between 1 and 2^31 - 1 elements, got shape %s" % (what, tuple(x.shape)))
-    return codes[x.dtype]
+    return code
 
 
 def _problem(x, b, axis):

@@ -34,8 +34,8 @@ def _problem(x, g, b, axis, segments):
     for t, what in ((x, "x"), (g, "g"), (b, "b")):
         if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
             raise RuntimeError("blocksparse_amd: %s must be a tensor on a ROCm device (no CPU fallback)" % what)
-    codes = {torch.float32: _lib.F32, torch.float16: _lib.F16, torch.bfloat16: _lib.BF16}
-    if x.dtype not in codes:
+    code = _lib.dtype_code(x.dtype)
+    if code is None:
         raise ValueError("layer_norm: x must be float32, float16 or bfloat16, got %s" % x.dtype)
     if x.dim() < 1 or x.numel() == 0:
         raise ValueError("layer_norm: x must have at least one dimension and one element, got shape %s" % (tuple(x.shape),))
@@ -52,7 +52,7 @@ def _problem(x, g, b, axis, segments):
     for t, what in ((g, "g"), (b, "b")):
         if t.dtype != torch.float32 or t.numel() != K or t.device != x.device:
             raise ValueError("layer_norm: %s must be a float32 tensor with %d elements on the device of x" % (what, K))
-    return (0 if axis == 0 else 1), K, N, segments, codes[x.dtype]
+    return (0 if axis == 0 else 1), K, N, segments, code
 
 
 def _args(device, ax, K, N, S, code, epsilon, relu, backward):

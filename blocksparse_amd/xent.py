@@ -29,10 +29,6 @@ except Exception:  # pragma: no cover
 XENT_F16_SCALE = _lib.XENT_F16_SCALE
 
 
-def _codes():
-    return {torch.float32: _lib.F32, torch.float16: _lib.F16, torch.bfloat16: _lib.BF16}
-
-
 def _label_types():
     return (torch.uint8, torch.int16, torch.int32, torch.int64)
 
@@ -42,12 +38,13 @@ def _problem(logits, what):
         raise RuntimeError("blocksparse_amd needs PyTorch-ROCm for device memory")
     if not isinstance(logits, torch.Tensor) or logits.device.type != "cuda":
         raise RuntimeError("blocksparse_amd: %s must be a tensor on a ROCm device (no CPU fallback)" % what)
-    if logits.dtype not in _codes():
+    code = _lib.dtype_code(logits.dtype)
+    if code is None:
         raise ValueError("softmax_cross_entropy: %s must be float32, float16 or bfloat16, got %s" % (what, logits.dtype))
     if logits.dim() < 1 or logits.numel() == 0:
         raise ValueError("softmax_cross_entropy: %s must have at least one dimension and one element, got shape %s" % (what, tuple(logits.shape)))
     K = int(logits.shape[-1])
-    return logits.numel() // K, K, _codes()[logits.dtype]
+    return logits.numel() // K, K, code
 
 
 def _labels32(labels, logits, N):

@@ -76,8 +76,13 @@ def test_list_sources_read_no_environment_and_keep_no_state():
     src = ""
     for f in ("bsmm_optim_list.hip", "bsmm_optim_list_kernels.h"):
         src += open(os.path.join(ROOT, "blocksparse_amd", "csrc", f)).read()
-    assert '#include "bsmm_optim_kernels.h"' in src and "adam_elem(" in src and "ema_elem(" in src and "opt_group_sum(" in src
-    assert "sqrtf" not in src                               # the arithmetic is called, not restated
+    # the per-tensor kernels' header holds the one body of every loop and the arithmetic it calls; the list sources call the bodies
+    kern = open(os.path.join(ROOT, "blocksparse_amd", "csrc", "bsmm_optim_kernels.h")).read()
+    assert '#include "bsmm_optim_kernels.h"' in src
+    for body in ("opt_adam_row", "opt_ema_row", "opt_sum_squared_row"):
+        assert kern.count("void %s(" % body) == 1 and "void %s(" % body not in src and body + "<" in src, body
+    assert "adam_elem(" in kern and "ema_elem(" in kern and "opt_group_sum(" in kern
+    assert "sqrtf" not in src and "adam_elem(" not in src and "ema_elem(" not in src      # the arithmetic is called, not restated
     src = re.sub(r"//[^\n]*", "", src)                     # (the comments may say what the code does not do)
     for word in ("getenv", "hipMalloc", "hipFree", "hipMemcpy", "Synchronize", "atomic", "static "):
         assert word not in src, word
