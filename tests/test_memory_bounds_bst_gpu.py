@@ -3,7 +3,8 @@ tests/test_memory_bounds_gpu.py -- the route the case is there for was taken, no
 element stored and none computed from poisoned memory, values within tests/test_bst_gpu.py's bars of oracle/bst_oracle.py -- for nt, nn, tn,
 masked softmax, its gradient and the fused scores + softmax pair, over that file's layouts: G.MATH_CASES, the ragged layout (empty query rows
 and key columns), block sizes 8 / 16 / 32 / 64, head states the fused kernel takes (32 / 64 / 128) and one it does not, a query row of
-exactly 20 blocks (the fused kernel's limit, NTS_MAXT tiles of four) and one of 21, which must take the two-launch route."""
+exactly 20 blocks (the fused kernel's limit, NTS_MAXT tiles of four) and one of 21, which must take the two-launch route, and the layouts of
+tests/_bst_long.py, whose query rows do not fit the register cache of the softmax kernels (the three-pass path)."""
 import os
 import sys
 
@@ -14,6 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, os.path.join(HERE, "golden"))
 import make_golden_bst as G
+import _bst_long as BL
 import _guard as GD
 from oracle import bst_oracle as O
 from oracle import bsmm_oracle as R
@@ -51,6 +53,10 @@ def _layout(key):
         return O.local_strided_layout(32)
     if key == "one":
         return np.ones((1, 1, 1), dtype=np.int32)
+    if key.startswith("long_rows_shared_b"):
+        return BL.long_rows_shared(int(key[len("long_rows_shared_b"):]))
+    if key.startswith("long_rows_b"):
+        return BL.long_rows(int(key[len("long_rows_b"):]))
     return G.layouts()[key]
 
 
@@ -73,6 +79,10 @@ BST_CASES.append(("row21-hs128-f32", "row21", 1, 32, 128, 1, None, "f32", "bf16"
 BST_CASES.append(("local32-hs64-bf16", "local32", 2, 32, 64, 2, "causal_o", "bf16", "bf16", True))
 BST_CASES.append(("local32-hs128-f16", "local32", 2, 32, 128, 1, "causal_o", "f16", "f16", True))
 BST_CASES.append(("one-hs64-f32", "one", 3, 32, 64, 1, None, "f32", "bf16", True))
+# query rows of N, N + 1 and 2N + 3 blocks (N = SmCache<VEC>::N of csrc/bst_kernels.h): the three-pass softmax and softmax gradient
+for bsize, hs, act in ((32, 64, "bf16"), (32, 64, "f16"), (64, 64, "bf16"), (8, 8, "bf16")):
+    BST_CASES.append(("long_rows-b%d-hs%d-%s" % (bsize, hs, act), "long_rows_b%d" % bsize, 2, bsize, hs, BL.batch_of(bsize), "head", act, act, False))
+BST_CASES.append(("long_rows_shared-b32-hs64-bf16", "long_rows_shared_b32", 3, 32, 64, 2, None, "bf16", "bf16", False))
 BST_IDS = [c[0] for c in BST_CASES]
 assert len(set(BST_IDS)) == len(BST_IDS)
 
