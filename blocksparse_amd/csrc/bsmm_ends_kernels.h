@@ -5,7 +5,7 @@
 //   xent_rows_kernel<V, R, NT>   rows that stay in registers: a team of NT lanes (64: a wave, four rows per workgroup, shuffles only; 256 or
 //                                1024: the workgroup, sums of the waves meet in LDS) holds R units per lane.  One read of x, one write of g.
 //   xent_long_kernel<V>          rows beyond that: 1024 lanes keep a running (max, sum) over their strips, meet once, and a second sweep
-//                                re-reads x and writes g.
+//                                re-reads x and writes g.  A -inf logit adds 0 to the sum, also while the lane's maximum is still -inf.
 //   xent_bwd_kernel<V>           dx = unscale(g) * dy[row] over the flat tensor.
 //   embed_fwd_kernel<VEC>        y rows as copies of 16 bytes (or of one element).
 //   embed_grad_chunks_kernel<V>  stage 1 of the gradient: a team of lanes sums one chunk of EMBED_CHUNK sorted positions of one column tile.
@@ -61,6 +61,12 @@ __device__ __forceinline__ float ends_team_sum(float v, float* lds) {
 // =====================================================================================================================================
 // softmax cross-entropy
 // =====================================================================================================================================
+// (sum of the other terms) / s for the label's element.  A label on a -inf logit has probability 0: the others ARE s, and the share is 1
+// exactly, which others * (1 / s) misses by an ulp for some s (a NaN s fails the comparison and stays NaN).
+__device__ __forceinline__ float xent_others_share(float others, float inv, float s, float xl) {
+    return (xl == -INFINITY && others == s) ? 1.f : others * inv;
+}
+
 // One row held in the registers of a team of NT lanes: lane t owns units t, t + NT, ... (R of them at most; K <= V * R * NT).
 template <class DT, int V, int R, int NT>
 __device__ __forceinline__ void xent_row_in_registers(const typename DT::T* xr, typename DT::T* gr, int K, int label, float* loss_row, int t,
@@ -115,7 +121,7 @@ __device__ __forceinline__ void xent_row_in_registers(const typename DT::T* xr, 
         }
     }
     // the label's element, by the lane that has just stored its unit (stores of one lane to one address keep their order)
-    if (t == (label / V) % NT) gr[label] = DT::from_f32(-(others * inv) * gscale);
+    if (t == (label / V) % NT) gr[label] = DT::from_f32(-xent_others_share(others, inv, s, xl) * gscale);
 }
 
 // grid: min(ceil(N / rows per workgroup), ENDS_MAX_GRID); block: NT = 64 -> 256 lanes (four rows at a time), else NT lanes (one row)
@@ -166,8 +172,15 @@ __global__ void __launch_bounds__(1024) xent_long_kernel(const typename DT::T* x
                 others *= exp2f((m - mu) * ENDS_LOG2E);  // (the first strip: m = -inf, the factor is 0 and the sum is 0)
                 m = mu;
             }
+            if (m > -INFINITY) {
 #pragma unroll
-            for (int e = 0; e < V; ++e) others += (u * V + e == label) ? 0.f : exp2f((v[e] - m) * ENDS_LOG2E);
+                for (int e = 0; e < V; ++e) others += (u * V + e == label) ? 0.f : exp2f((v[e] - m) * ENDS_LOG2E);
+            } else {
+                // the lane has met no finite logit yet: this unit holds -inf (a class of probability 0: it adds 0, where the difference
+                // above would be -inf - -inf = NaN) or NaN, which still makes the sum NaN
+#pragma unroll
+                for (int e = 0; e < V; ++e) others += (u * V + e == label || v[e] == -INFINITY) ? 0.f : exp2f((v[e] - m) * ENDS_LOG2E);
+            }
         }
         const float M = ends_team_max<NT>(m, lds);
         others = (m == -INFINITY) ? 0.f : others * exp2f((m - M) * ENDS_LOG2E);
@@ -182,7 +195,7 @@ __global__ void __launch_bounds__(1024) xent_long_kernel(const typename DT::T* x
             for (int e = 0; e < V; ++e) v[e] = (exp2f((v[e] - M) * ENDS_LOG2E) * inv) * gscale;
             vec_store<DT, V>(gr + (size_t)u * V, v);
         }
-        if (t == (label / V) % NT) gr[label] = DT::from_f32(-(others * inv) * gscale);
+        if (t == (label / V) % NT) gr[label] = DT::from_f32(-xent_others_share(others, inv, s, xl) * gscale);
     }
 }
 

@@ -88,7 +88,7 @@ int forward(const void* xv, const float* g, const float* b, void* yv, float* mea
     const A0Cut c = a0_cut(Ks, N, a->dtype);
     float* ws = static_cast<float*>(a->workspace);
     BSMM_LAUNCH((ln_stats_a0_kernel<DT, VEC>), (unsigned)(c.strips * c.split * S), 256, st, x, ws, N, S, Ks, c.strips, c.split, c.rps);
-    BSMM_LAUNCH((ln_stats_merge_a0_kernel<DT>), (unsigned)(((long long)S * N + 255) / 256), 256, st, x, ws, mean, rstd, N, S, Ks, c.split, a->epsilon);
+    BSMM_LAUNCH(ln_stats_merge_a0_kernel, (unsigned)(((long long)S * N + 255) / 256), 256, st, ws, mean, rstd, N, S, Ks, c.split, c.rps, a->epsilon);
     BSMM_LAUNCH((ln_norm_a0_kernel<DT, VEC>), (unsigned)(c.strips * c.tiles * S), 256, st, x, g, b, mean, rstd, y, N, Ks, c.strips, c.tiles, a->relu);
     return BSMM_OK;
 }

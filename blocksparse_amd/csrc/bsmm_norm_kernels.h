@@ -6,23 +6,24 @@
 //     ln_fwd_a1_kernel<G>   one group of G lanes per row -- a wave (G = 64) for Ks <= 2048, a workgroup (G = 256) for Ks <= 8192: a lane keeps
 //                           LN_LANE_ELEMS = 32 elements in registers, x is read ONCE.  Mean first, then the mean of squared deviations
 //                           from the registers (the two-pass form).
-//     ln_fwd_a1_long_kernel Ks > 8192 = LN_ROW_LIMIT: a workgroup streams the row twice (the plain sum for the mean and squares shifted by the
-//                           row's first element for the variance, then the normalise pass; the second read comes from L2).
+//     ln_fwd_a1_long_kernel Ks > 8192 = LN_ROW_LIMIT: a workgroup streams the row three times (the sum for the mean, the squared deviations
+//                           from that mean, then the normalise pass; the second and third read come from L2): the two-pass form as well.
 //     ln_bwd_a1_kernel<G>   same shapes; a group walks rows n, n + stride, ...: per row the two per-sample sums and dx from registers, and
 //                           across its rows the dg / db contributions of the lane's own 32 columns in 64 accumulators, stored once at the
 //                           end as one row of partials.  x and dy are read ONCE.
-//     ln_bwd_a1_long_kernel + ln_dgdb_a1_kernel   Ks > 8192: rows streamed twice; dg / db partials by a column walk of their own.
+//     ln_bwd_a1_long_kernel + ln_dgdb_a1_kernel   Ks > 8192: rows streamed twice; dg / db partials by a column walk of their own (dg in
+//                           fp64 within a partial, see ln_dg_term).
 //   feature axis 0, x (K, N): the reduction runs down a stride-N column.  A workgroup owns a strip of 64 * V contiguous columns and a slice
 //   of a segment's rows; its four waves take every fourth row, a lane owns V columns and keeps their sums in registers, the waves meet in
 //   LDS (sp_reduce_a0_kernel of bsmm_sparsity_kernels.h reads this layout the same way).  A segment's rows are cut into `split` slices so
 //   that a few strips still fill the chip; the slices' partial sums go to the workspace and a merge kernel adds them in ascending order.
-//     ln_stats_a0_kernel    sum x and sum (x - c)^2 with c = the column's first row of the segment: every slice shifts by the same c, so
-//                           partials simply add; mean = sum x / Ks, var = sum (x - c)^2 / Ks - (mean - c)^2: the SHIFTED values have a mean
-//                           within a few standard deviations of zero (this is not E[x^2] - mean^2 of the raw values).
-//     ln_stats_merge_a0_kernel -> mean, rstd;  ln_norm_a0_kernel: the normalise pass, every CU busy whatever the strip count; it re-reads
-//                           x from L2 / Infinity Cache.
+//     ln_stats_a0_kernel    per slice: sum x, then sum (x - the slice's mean)^2 in a second pass over the slice (two-pass within the slice;
+//                           the rows come from L1 / L2 the second time).  ln_stats_merge_a0_kernel adds the slices' sums -> mean, and joins
+//                           their squared deviations about that mean: each slice's own plus rows * (slice mean - mean)^2, all terms
+//                           >= 0.  No term depends on which row of the segment comes first.
+//     ln_norm_a0_kernel     the normalise pass, every CU busy whatever the strip count; it re-reads x from L2 / Infinity Cache.
 //     ln_bwd_sums_a0_kernel the per-sample sums (partials per slice) and, per row, the strip's dg / db contribution by a wave reduction
-//                           (partials per strip);  ln_sums_merge_a0_kernel;  ln_bwd_dx_a0_kernel writes dx.
+//                           (partials per strip; dg in fp64 within a strip);  ln_sums_merge_a0_kernel;  ln_bwd_dx_a0_kernel writes dx.
 //   ln_sum_partials_kernel  dg / db = the partial rows added in ascending order (four slices per output, joined in LDS in a fixed order).
 #pragma once
 #include "bsmm_vec.h"
@@ -51,6 +52,14 @@ __device__ __forceinline__ float ln_group_sum(float v, float* red) {
         v = (red[0] + red[1]) + (red[2] + red[3]);
     }
     return v;
+}
+
+// acc + d * (x - mean) * rstd in fp64, for the dg of the kernels in which one thread or one wave sums a feature over the samples
+// (ln_dgdb_a1_kernel, ln_bwd_sums_a0_kernel); the partial is rounded to fp32 once, when it is stored.  A feature whose dg is hundreds of
+// times the mean |dg| (an outlier feature: xhat = 90 in every sample) otherwise carries three fp32 roundings per term and lands about one fp32
+// step of its own value away, which is several 1e-5 of the mean |dg|.  The fp32 xhat that masks dy and feeds dx is unchanged.
+__device__ __forceinline__ double ln_dg_term(float d, float x, float mean, float rstd, double acc) {
+    return fma((double)d, ((double)x - (double)mean) * (double)rstd, acc);
 }
 
 // ---- V consecutive elements <-> V floats; VEC: one 16-byte access (bsmm_vec.h), all V valid; else element accesses, those at or beyond lim skipped ----
@@ -164,21 +173,24 @@ __global__ void __launch_bounds__(256) ln_fwd_a1_long_kernel(const typename DT::
     const long long rs = blockIdx.x;
     const int n = (int)(rs / S), s = (int)(rs - (long long)n * S);
     const typename DT::T* xr = x + (size_t)rs * Ks;
-    const float c0 = DT::to_f32(xr[0]);
     float s1 = 0.f, s2 = 0.f;
+    for (int e = threadIdx.x * V; e < Ks; e += 256 * V) {
+        float v[V];
+        ln_load<DT, VEC>(xr + e, Ks - e, v);                 // (elements past the row read as zero)
+#pragma unroll
+        for (int j = 0; j < V; ++j) s1 += v[j];
+    }
+    const float m = ln_group_sum<256>(s1, red) / (float)Ks;
     for (int e = threadIdx.x * V; e < Ks; e += 256 * V) {
         float v[V];
         ln_load<DT, VEC>(xr + e, Ks - e, v);
 #pragma unroll
         for (int j = 0; j < V; ++j) {
-            const float d = e + j < Ks ? v[j] - c0 : 0.f;
-            s1 += v[j];
+            const float d = e + j < Ks ? v[j] - m : 0.f;
             s2 = fmaf(d, d, s2);
         }
     }
-    const float m = ln_group_sum<256>(s1, red) / (float)Ks, md = m - c0;
-    const float var = fmaxf(ln_group_sum<256>(s2, red) / (float)Ks - md * md, 0.f);
-    const float r = 1.f / sqrtf(var + eps);
+    const float r = 1.f / sqrtf(ln_group_sum<256>(s2, red) / (float)Ks + eps);
     if (threadIdx.x == 0) {
         mean[(size_t)s * N + n] = m;
         rstd[(size_t)s * N + n] = r;
@@ -336,15 +348,17 @@ __global__ void __launch_bounds__(256) ln_dgdb_a1_kernel(const typename DT::T* _
     if (k >= K) return;
     const int s = k / Ks;
     const float gk = g[k], bk = relu ? b[k] : 0.f;
-    float adg = 0.f, adb = 0.f;
+    double adg = 0.0;                                      // (fp64, rounded once below: see ln_dg_term)
+    float adb = 0.f;
     for (int n = p; n < N; n += P) {
-        const float xhat = (DT::to_f32(x[(size_t)n * K + k]) - mean[(size_t)s * N + n]) * rstd[(size_t)s * N + n];
+        const float xv = DT::to_f32(x[(size_t)n * K + k]), m = mean[(size_t)s * N + n], r = rstd[(size_t)s * N + n];
+        const float xhat = (xv - m) * r;
         float d = DT::to_f32(dy[(size_t)n * K + k]);
         if (relu && !(fmaf(xhat, gk, bk) > 0.f)) d = 0.f;
-        adg = fmaf(d, xhat, adg);
+        adg = ln_dg_term(d, xv, m, r, adg);
         adb += d;
     }
-    part[((size_t)p * 2) * K + k] = adg;
+    part[((size_t)p * 2) * K + k] = (float)adg;
     part[((size_t)p * 2 + 1) * K + k] = adb;
 }
 
@@ -453,8 +467,13 @@ __device__ __forceinline__ void ln_join_waves(float (*lds)[2][V][64], const floa
     }
 }
 
-// grid: strips * S * split workgroups (strip fastest).  ws[(sp * S + s)][2][N]: sum x, sum (x - c)^2 over rows [sp * rps, (sp + 1) * rps) of
-// segment s, c = row 0 of the segment.
+// rows of slice sp of a segment of Ks rows cut into slices of rps rows (the last slices of a long segment may be empty)
+__device__ __forceinline__ int ln_slice_rows(int Ks, int rps, int sp) {
+    return max(min(Ks, (sp + 1) * rps) - sp * rps, 0);
+}
+
+// grid: strips * S * split workgroups (strip fastest).  ws[(sp * S + s)][2][N] over the rows [sp * rps, (sp + 1) * rps) of segment s:
+// [0] sum x, [1] sum (x - the SLICE's mean)^2 -- two passes over the slice, the second from L1 / L2, which it has just been read into.
 template <class DT, bool VEC>
 __global__ void __launch_bounds__(256) ln_stats_a0_kernel(const typename DT::T* __restrict__ x, float* __restrict__ ws, int N, int S, int Ks, int strips,
                                                           int split, int rps) {
@@ -464,44 +483,75 @@ __global__ void __launch_bounds__(256) ln_stats_a0_kernel(const typename DT::T* 
     const int strip = blockIdx.x % strips, rest = blockIdx.x / strips, s = rest % S, sp = rest / S;
     const int n0 = strip * 64 * V;
     const typename DT::T* xs = x + (size_t)s * Ks * N;
-    float c[V], s1[V], s2[V];
-    ln_load_row<DT, VEC>(xs, n0, lane, N, c);
+    const int k0 = sp * rps, rows = ln_slice_rows(Ks, rps, sp), k1 = k0 + rows;
+    float s1[V], s2[V], m[V];
 #pragma unroll
     for (int j = 0; j < V; ++j) s1[j] = s2[j] = 0.f;
-    const int k1 = min(Ks, (sp + 1) * rps);
 #pragma unroll 4
-    for (int k = sp * rps + w; k < k1; k += 4) {
+    for (int k = k0 + w; k < k1; k += 4) {
+        float v[V];
+        ln_load_row<DT, VEC>(xs + (size_t)k * N, n0, lane, N, v);
+#pragma unroll
+        for (int j = 0; j < V; ++j) s1[j] += v[j];
+    }
+    // every wave gets the four waves' sums (wave order 0, 1, 2, 3) and so the slice's mean of its columns
+#pragma unroll
+    for (int j = 0; j < V; ++j) lds[w][0][j][lane] = s1[j];
+    __syncthreads();
+    const float rrows = 1.f / (float)max(rows, 1);
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+        s1[j] = ((lds[0][0][j][lane] + lds[1][0][j][lane]) + lds[2][0][j][lane]) + lds[3][0][j][lane];
+        m[j] = s1[j] * rrows;
+    }
+#pragma unroll 4
+    for (int k = k0 + w; k < k1; k += 4) {
         float v[V];
         ln_load_row<DT, VEC>(xs + (size_t)k * N, n0, lane, N, v);
 #pragma unroll
         for (int j = 0; j < V; ++j) {
-            const float d = v[j] - c[j];
-            s1[j] += v[j];
+            const float d = v[j] - m[j];
             s2[j] = fmaf(d, d, s2[j]);
         }
     }
-    float* out = ws + ((size_t)sp * S + s) * 2 * N;
-    ln_join_waves<V, VEC>(lds, s1, s2, out, out + N, n0, N);
+#pragma unroll
+    for (int j = 0; j < V; ++j) lds[w][1][j][lane] = s2[j];
+    __syncthreads();
+    if (w == 0) {
+        float* out = ws + ((size_t)sp * S + s) * 2 * N;
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            const int n = ln_col<V, VEC>(n0, lane, j);
+            if (n < N) {
+                out[n] = s1[j];
+                out[N + n] = ((lds[0][1][j][lane] + lds[1][1][j][lane]) + lds[2][1][j][lane]) + lds[3][1][j][lane];
+            }
+        }
+    }
 }
 
-// one thread per (s, n): the slices' sums in ascending order -> mean, rstd
-template <class DT>
-__global__ void __launch_bounds__(256) ln_stats_merge_a0_kernel(const typename DT::T* __restrict__ x, const float* __restrict__ ws, float* __restrict__ mean,
-                                                                float* __restrict__ rstd, int N, int S, int Ks, int split, float eps) {
+// one thread per (s, n), the slices in ascending order: mean = sum of the slices' sums / Ks, and the squared deviations from THAT mean
+// are, exactly, each slice's own (about its own mean) plus rows * (slice mean - mean)^2: every term is >= 0, nothing cancels
+__global__ void __launch_bounds__(256) ln_stats_merge_a0_kernel(const float* __restrict__ ws, float* __restrict__ mean, float* __restrict__ rstd, int N, int S,
+                                                                int Ks, int split, int rps, float eps) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= (long long)S * N) return;
     const int s = (int)(i / N), n = (int)(i - (long long)s * N);
-    float s1 = 0.f, s2 = 0.f;
+    // (unrolled: the loads of eight slices are in flight together; the adds keep their ascending order)
+    float s1 = 0.f;
+#pragma unroll 8
+    for (int sp = 0; sp < split; ++sp) s1 += ws[((size_t)sp * S + s) * 2 * N + n];
+    const float m = s1 / (float)Ks;
+    float s2 = 0.f;
+#pragma unroll 8
     for (int sp = 0; sp < split; ++sp) {
         const float* p = ws + ((size_t)sp * S + s) * 2 * N + n;
-        s1 += p[0];
-        s2 += p[N];
+        const int rows = ln_slice_rows(Ks, rps, sp);
+        const float d = p[0] * (1.f / (float)max(rows, 1)) - m;
+        s2 += fmaf((float)rows * d, d, p[N]);
     }
-    const float c = DT::to_f32(x[(size_t)s * Ks * N + n]);
-    const float m = s1 / (float)Ks, md = m - c;
-    const float var = fmaxf(s2 / (float)Ks - md * md, 0.f);
     mean[i] = m;
-    rstd[i] = 1.f / sqrtf(var + eps);
+    rstd[i] = 1.f / sqrtf(s2 / (float)Ks + eps);
 }
 
 // grid: strips * ceil(Ks / LN_A0_ROWS) * S workgroups (strip fastest); wave w takes rows w, w + 4, ... of the workgroup's LN_A0_ROWS
@@ -557,13 +607,14 @@ __global__ void __launch_bounds__(256) ln_bwd_sums_a0_kernel(const typename DT::
         float xv[V], dv[V];
         ln_load_row<DT, VEC>(x + f * N, n0, lane, N, xv);
         ln_load_row<DT, VEC>(dy + f * N, n0, lane, N, dv);
-        float rdg = 0.f, rdb = 0.f;
+        double rdg = 0.0;                                  // (fp64, rounded once below: see ln_dg_term)
+        float rdb = 0.f;
 #pragma unroll
         for (int j = 0; j < V; ++j) {                      // (columns outside: x = dy = mean = rstd = 0, so xhat = d = 0)
             const float xhat = (xv[j] - m[j]) * r[j];
             float d = dv[j];
             if (relu && !(fmaf(xhat, gk, bk) > 0.f)) d = 0.f;
-            rdg = fmaf(d, xhat, rdg);
+            rdg = ln_dg_term(d, xv[j], m[j], r[j], rdg);
             rdb += d;
             const float dg_ = d * gk;
             s1[j] = fmaf(xhat, dg_, s1[j]);
@@ -572,7 +623,7 @@ __global__ void __launch_bounds__(256) ln_bwd_sums_a0_kernel(const typename DT::
         rdg = wave_sum(rdg);
         rdb = wave_sum(rdb);
         if (lane == 0) {
-            part[((size_t)strip * 2) * K + f] = rdg;
+            part[((size_t)strip * 2) * K + f] = (float)rdg;
             part[((size_t)strip * 2 + 1) * K + f] = rdb;
         }
     }

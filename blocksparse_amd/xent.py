@@ -9,7 +9,9 @@ The reference's name and arguments (blocksparse/transformer.py:685-700) over the
     dx = softmax_cross_entropy_bwd(g, dloss)                        # dx like g; out=g writes over the stash
 
 ``labels`` may be uint8, int16, int32 or int64; a label outside [0, K) marks an ignored row (padding): its loss and its gradient are zero.
-The loss is ``log(sum exp(x - max)) + max - x[label]`` in fp32 -- not clipped like the reference's ``-log(max(p, 2^-24))``.  An fp16 stash
+The loss is ``log(sum exp(x - max)) + max - x[label]`` in fp32 -- not clipped like the reference's ``-log(max(p, 2^-24))``.  A logit of
+``-inf`` is a class of probability 0 (a masked class): its ``g`` is exactly 0, and a label on it gives the loss ``+inf`` and ``g[label] = -1``;
+a row with no finite logit, or with ``+inf`` or NaN in it, gives NaN in that row only.  An fp16 stash
 holds ``XENT_F16_SCALE * (p - onehot)``; the backward undoes the scale.  The autograd function saves the stash, not the logits, and never
 works in place.  PyTorch is plumbing (memory, streams, autograd); there is no CPU fallback.
 

@@ -20,6 +20,10 @@
  *            keeps it finite, and probabilities below 2^-14 keep their bits); bf16 and fp32 are unscaled.
  *            The label's element is computed as -(sum of the other terms) / s, not as p - 1: it keeps its bits when p is close to 1.
  * A label outside [0, K) marks an ignored row (padding): loss = 0 and every g_k = 0.
+ * Non-finite logits.  x_k = -inf is a class of probability 0 (a masked class, the padding of a vocabulary): it adds nothing to s and its
+ * g_k is exactly 0 on every path, wherever it lies in the row.  A label on such a class gives loss = +inf and g[label] = -1 exactly (the
+ * stored value is -BSMM_XENT_F16_SCALE for fp16).  A row with no finite logit, or with a +inf or a NaN anywhere, gives a NaN loss (and g) in
+ * THAT row; no other row is touched, also where several rows share a workgroup.
  * Backward:   dx_k = round(unscale(g_k) * dy[n]),   the unscale (x 2^-15 for fp16, exact) and the product in fp32.
  * Aliasing that is part of the contract: g may be the pointer x (the forward in place over the logits), and dx may be the pointer g.  Any
  * other overlap is undefined.

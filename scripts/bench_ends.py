@@ -5,6 +5,7 @@ torch composition and writes a markdown table:
 
   xent-bytes   N = 65536 x K = 256 (a byte-level vocabulary), bf16
   xent-words   N = 8192 x K = 32768 (a word-level one), bf16
+  xent-long    N = 2048 x K = 65536, bf16: rows beyond the registers, the streamed kernel (BSMM_XENT_LONG)
   embed-bytes-skew / embed-bytes-tiled      C = 256,   K = 1024, nIdx = 65536, bf16
   embed-words-skew / embed-words-tiled      C = 50257, K = 1024, nIdx = 65536, bf16
       skew: a seeded byte-like histogram (one index holds about a sixth, the rest fall off like 1 / rank); tiled: arange(1024) tiled over
@@ -27,12 +28,12 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-XENT = {"xent-bytes": (65536, 256), "xent-words": (8192, 32768)}
+XENT = {"xent-bytes": (65536, 256), "xent-words": (8192, 32768), "xent-long": (2048, 65536)}
 EMBED = {"embed-bytes-skew": (256, "skew"), "embed-bytes-tiled": (256, "tiled"), "embed-words-skew": (50257, "skew"), "embed-words-tiled": (50257, "tiled")}
 EK, ENIDX, CTX = 1024, 65536, 1024
 BOUND = "xent-fp32-bound"
 BOUND_SHAPES = ((64, 256), (16, 1031), (8, 8192), (4, 32768), (2, 70001))
-ORDER = ("xent-bytes", "xent-words", "embed-bytes-skew", "embed-bytes-tiled", "embed-words-skew", "embed-words-tiled", BOUND)
+ORDER = ("xent-bytes", "xent-words", "xent-long", "embed-bytes-skew", "embed-bytes-tiled", "embed-words-skew", "embed-words-tiled", BOUND)
 
 
 def _time(torch, fn, window):

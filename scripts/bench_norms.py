@@ -2,7 +2,8 @@
 
     python scripts/bench_norms.py --out profiles/norms_bench.md
 
-Shapes: the headline activation, 4096 features x 8192 samples in bf16, in both layouts, and the small minibatch N = 64 on feature axis 0;
+Shapes: the headline activation, 4096 features x 8192 samples in bf16, in both layouts, the small minibatch N = 64 on feature axis 0, and
+rows of 16384 features on axis 1, which are streamed rather than kept in registers;
 ReLU fused on our side, a separate ``relu`` on torch's.  Every shape runs in a child process of its own under a time limit (``--case`` is
 the child's entry); the parent stops at the first child that fails.  Each timed function is captured into a graph of ``INNER`` calls (no
 host time between launches), warmed up, and replayed in windows of at least ``--window`` seconds between device events; the figure is the
@@ -28,6 +29,7 @@ CASES = {
     "axis0-N8192": (4096, 8192, 0, "bf16"),
     "axis1-N8192": (4096, 8192, 1, "bf16"),
     "axis0-N64": (4096, 64, 0, "bf16"),
+    "axis1-K16384": (16384, 2048, 1, "bf16"),
 }
 
 
@@ -151,7 +153,7 @@ def main():
         print("RESULT " + json.dumps(run_case(a.case, a.window, a.repeats)))
         return 0
     results = []
-    for name in ("axis0-N8192", "axis1-N8192", "axis0-N64"):
+    for name in ("axis0-N8192", "axis1-N8192", "axis0-N64", "axis1-K16384"):
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "--case", name, "--window", str(a.window), "--repeats", str(a.repeats)],
                            capture_output=True, text=True, timeout=a.timeout)
         line = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")]

@@ -111,6 +111,114 @@ def test_xent_against_float64(env, case, dtype, dist):
     assert dx2 is gs and torch.equal(dx2, dx), (ctx, "backward in place")
 
 
+# (K, elements off a 16-byte boundary, the path): every path, both access widths
+MASKED_CASES = [(10, 0, S), (520, 0, S | V), (1024, 1, S), (1032, 0, R | V), (4097, 0, W), (8200, 0, W | V), (16385, 0, G), (32776, 0, G | V),
+                (32776, 1, G)]
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("case", MASKED_CASES, ids=["K%d-off%d" % c[:2] for c in MASKED_CASES])
+def test_xent_masked_classes_against_float64(env, case, dtype):
+    """Classes masked with -inf (tests/_ends_ref.py xent_masked_inputs: six rows, one pattern each) have probability 0.  The loss at the
+    fp32 bars over the rows whose float64 loss is finite; the row whose label names a masked class has loss +inf and g[label] = -scale
+    exactly; g of every masked class is exactly 0 (it is exp2(-inf) / s); every other element by the criteria of
+    test_xent_against_float64, unchanged; the same bits from a second call and from the call in place.
+    The streamed kernel once started every lane's running maximum at -inf and added exp2((-inf) - (-inf)) = NaN for a unit of masked
+    classes read before any finite one: rows head, unit0 and single (and whatever else puts a masked unit first in a lane) came back NaN."""
+    torch, xent, _ = env
+    K, off, path = case
+    X, labels = ER.xent_masked_inputs(K, dtype)
+    wloss, wg, wp, wdist = ER.xent_ref(X, labels)
+    scale = ER.stash_scale(dtype)
+    ctx = (case, dtype)
+    hot = ER.MASKED_LABEL_ROW
+    fin_rows = np.isfinite(wloss)
+    assert fin_rows.sum() == len(ER.MASKS) - 1 and wloss[hot] == np.inf
+    x = _place(torch, X, dtype, off)
+    lab = torch.from_numpy(labels).to("cuda")
+    out = _empty(torch, x, off)
+    assert xent.xent_path(x, out) == path and xent.xent_path(x) == path, (ctx, xent.xent_path(x, out))
+    loss, g = xent.softmax_cross_entropy_fwd(x, lab, out=out)
+    assert np.array_equal(P.to_host(x), X)
+    hloss, got = P.to_host(loss), P.to_host(g)
+    print("%s: loss %s" % (ctx, hloss))
+    assert np.isfinite(hloss[fin_rows]).all(), (ctx, "loss of rows", [ER.MASKS[i] for i in np.nonzero(~np.isfinite(hloss) & fin_rows)[0]])
+    l2, mx = P.errors(hloss[fin_rows], wloss[fin_rows])
+    print("%s: loss L2 %.2e max %.2e" % (ctx, l2, mx))
+    assert l2 <= P.L2_BAR["f32"] and mx <= P.MAX_BAR["f32"], (ctx, "loss", l2, mx)
+    assert hloss[hot] == np.inf, (ctx, "loss of a masked label", hloss[hot])
+    finite = np.isfinite(X)
+    assert not np.isnan(got).any(), (ctx, "NaN in g of rows", [ER.MASKS[i] for i in np.nonzero(np.isnan(got).any(axis=1))[0]])
+    assert not got[~finite & (wg == 0)].any(), (ctx, "g of a masked class")
+    assert got[hot, labels[hot]] == -scale and wg[hot, labels[hot]] == -1.0, (ctx, "g of the masked label", got[hot, labels[hot]])
+    if dtype == "f32":
+        ratio, at = ER.f32_g_ratio(got, wg, wp, wdist, finite)
+        print("%s: fp32 g worst ratio to the bound %.3f at finite element %d" % (ctx, ratio, at))
+        assert ratio <= 1.0, (ctx, "fp32 g beyond its bound", ratio, at)
+    else:
+        ER.check_16bit(got, wg * scale, dtype, (ctx, "g"), finite)
+    loss2, g2 = xent.softmax_cross_entropy_fwd(x, lab, out=_empty(torch, x, off))
+    assert torch.equal(loss2, loss) and torch.equal(g2, g), (ctx, "forward twice")
+    xin = _empty(torch, x, off)
+    xin.copy_(x)
+    assert xent.xent_path(xin, xin) == path
+    loss3, g3 = xent.softmax_cross_entropy_fwd(xin, lab, out=xin)
+    assert g3 is xin and torch.equal(loss3, loss) and torch.equal(g3, g), (ctx, "forward in place")
+
+
+@pytest.mark.parametrize("dtype", ("bf16", "f32"))
+@pytest.mark.parametrize("K", (256, 16385))
+def test_xent_nonfinite_row_stays_in_its_row(env, K, dtype):
+    """+inf in row 2, NaN in row 5, row 6 all -inf: those rows' losses are NaN, as the float64 definition gives, and every other row's loss
+    and g keep the bits of a call on the clean tensor (the short path shares a workgroup between four rows)."""
+    torch, xent, _ = env
+    N = 8
+    X, _, _ = ER.xent_inputs(N, K, dtype, "uniform")
+    labels = (np.arange(N) * 37 + 11) % K
+    bad = X.copy()
+    bad[2, K // 3] = np.inf
+    bad[5, K - 2] = np.nan
+    bad[6, :] = -np.inf
+    with np.errstate(invalid="ignore"):
+        wloss = ER.xent_ref(bad, labels)[0]
+    dirty = np.array([2, 5, 6])
+    clean = np.setdiff1d(np.arange(N), dirty)
+    assert np.isnan(wloss[dirty]).all() and np.isfinite(wloss[clean]).all()
+    lab = torch.from_numpy(labels).to("cuda")
+    want_loss, want_g = xent.softmax_cross_entropy_fwd(P.to_dev(X, dtype, torch), lab)
+    loss, g = xent.softmax_cross_entropy_fwd(P.to_dev(bad, dtype, torch), lab)
+    assert xent.xent_path(g) & 255 == (S if K == 256 else G)
+    assert torch.isnan(loss[torch.from_numpy(dirty).to("cuda")]).all(), (K, dtype, P.to_host(loss))
+    rows = torch.from_numpy(clean).to("cuda")
+    assert torch.equal(loss[rows], want_loss[rows]) and torch.equal(g[rows], want_g[rows]), (K, dtype, "a clean row changed")
+    l2, mx = P.errors(P.to_host(loss)[clean], wloss[clean])
+    assert l2 <= P.L2_BAR["f32"] and mx <= P.MAX_BAR["f32"], (K, dtype, l2, mx)
+
+
+@pytest.mark.parametrize("K,path", ((4097, W), (16385, G)))
+def test_xent_strided_long_rows(env, K, path):
+    """More rows than the grid has workgroups on the two paths for long rows: 7 base rows, checked against float64 in a call of their own,
+    tiled on the device to N = 2049.  Row r keeps the bits of base row r % 7; only the base rows ever reach the host."""
+    torch, xent, _ = env
+    base, N = 7, 2049
+    X, labels, _ = ER.xent_inputs(base, K, "bf16", "uniform")
+    wloss, wg, _, _ = ER.xent_ref(X, labels)
+    x7 = P.to_dev(X, "bf16", torch)
+    lab7 = torch.from_numpy(labels).to("cuda")
+    assert xent.xent_path(x7) == path
+    loss7, g7 = xent.softmax_cross_entropy_fwd(x7, lab7)
+    l2, mx = P.errors(P.to_host(loss7), wloss)
+    assert l2 <= P.L2_BAR["f32"] and mx <= P.MAX_BAR["f32"], (K, l2, mx)
+    ER.check_16bit(P.to_host(g7), wg, "bf16", (K, "g of the base rows"))
+    reps = (N + base - 1) // base
+    x = x7.repeat(reps, 1)[:N].contiguous()
+    lab = lab7.repeat(reps)[:N].contiguous()
+    assert xent.xent_path(x) == path | T, xent.xent_path(x)
+    loss, g = xent.softmax_cross_entropy_fwd(x, lab)
+    assert torch.equal(loss, loss7.repeat(reps)[:N]), (K, "loss")
+    assert torch.equal(g, g7.repeat(reps, 1)[:N]), (K, "g")
+
+
 @pytest.mark.parametrize("ltype", ("uint8", "int16", "int32", "int64"))
 def test_xent_label_dtypes(env, ltype):
     torch, xent, _ = env

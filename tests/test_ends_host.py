@@ -280,3 +280,96 @@ def test_seeded_inputs_hold_what_the_gpu_tests_rely_on():
     assert {-1, 50, 1 << 30} <= set(out.tolist())
     W, DY, DYX = ER.embed_values(50, 96, 300, "bf16")
     assert np.array_equal(DYX * 32, np.round(DYX * 32)) and np.abs(DYX).max() < 4
+
+
+MASKED_KS = (10, 520, 1024, 1032, 4097, 8200, 16385, 32776)      # the K of the GPU test's cases
+
+
+def test_xent_ref_indexes_the_label_and_keeps_its_bits_on_finite_inputs():
+    """xent_ref once took x[label] as (x * onehot).sum(), which is NaN for a masked class; it indexes now.  On the seeded finite inputs
+    of the GPU tests nothing may move by a bit."""
+    def old(X, labels):
+        x = np.asarray(X, dtype=np.float64)
+        N, K = x.shape
+        live = (labels >= 0) & (labels < K)
+        m = x.max(axis=1)
+        lse = m + np.log(np.exp(x - m[:, None]).sum(axis=1))
+        p = np.exp(x - lse[:, None])
+        onehot = np.zeros((N, K))
+        onehot[np.nonzero(live)[0], labels[live]] = 1.0
+        return np.where(live, lse - (x * onehot).sum(axis=1), 0.0), np.where(live[:, None], p - onehot, 0.0), p, np.abs(x - m[:, None])
+
+    for N, K in ((1, 1), (3, 10), (64, 256), (5, 257), (16, 1031), (3, 4097), (2, 16385), (2, 32776), (7, 4097)):
+        for dtype in ("f32", "f16", "bf16"):
+            for dist in ("normal", "uniform"):
+                X, labels, _ = ER.xent_inputs(N, K, dtype, dist)
+                for a, b in zip(ER.xent_ref(X, labels), old(X, labels)):
+                    assert a.dtype == b.dtype == np.float64 and np.array_equal(a.view(np.int64), b.view(np.int64)), (N, K, dtype, dist)
+    # the mask of the finite logits leaves the two criteria as they were when every logit is finite
+    X, labels, _ = ER.xent_inputs(5, 257, "bf16", "uniform")
+    _, g, p, dist = ER.xent_ref(X, labels)
+    got = ER.rounded(g, "f32")
+    assert ER.f32_g_ratio(got, g, p, dist) == ER.f32_g_ratio(got, g, p, dist, np.isfinite(X))
+    ER.check_16bit(ER.rounded(g, "bf16"), g, "bf16", "mask of all", np.isfinite(X))
+
+
+def test_masked_inputs_and_their_float64_reference():
+    from blocksparse_amd import xent
+    hot = ER.MASKED_LABEL_ROW
+    for K in MASKED_KS:
+        for dtype in ("f32", "f16", "bf16"):
+            X, labels = ER.xent_masked_inputs(K, dtype)
+            off = np.isneginf(X)
+            assert X.shape == (6, K) and not np.isnan(X).any() and not np.isposinf(X).any() and np.array_equal(ER.rounded(X, dtype), X)
+            assert (off.sum(axis=1) >= 1).all() and ((~off).sum(axis=1) >= 1).all()
+            row = dict(zip(ER.MASKS, off))
+            head = min(8 * 1024, K - 1)
+            assert row["head"][:head].all() and not row["head"][head:].any()
+            assert row["tail"][K - K // 3:].all() and not row["tail"][:K - K // 3].any()
+            assert row["stripes"][:8].all() and (K < 16 or not row["stripes"][8:16].any())
+            assert row["unit0"].sum() == min(8, K - 1) and row["unit0"][:min(8, K - 1)].all()
+            assert row["single"].sum() == 1 and row["single"][5]
+            assert (~row["only_label"]).sum() == 1 and not row["only_label"][labels[5]]
+            masked_label = off[np.arange(6), labels]
+            assert masked_label.tolist() == [i == hot for i in range(6)]
+            loss, g, p, dist = ER.xent_ref(X, labels)
+            assert np.isfinite(np.delete(loss, hot)).all() and loss[hot] == np.inf and (np.delete(loss, hot) >= 0).all()
+            assert np.isfinite(g).all() and np.isfinite(p).all() and not p[off].any() and np.isinf(dist[off]).all() and np.isfinite(dist[~off]).all()
+            assert g[hot, labels[hot]] == -1.0 and not g[off & (np.arange(K)[None, :] != labels[:, None])].any()
+            assert np.allclose(p.sum(axis=1), 1.0, rtol=0, atol=1e-12) and abs(loss[5]) < 1e-12
+            # the package's float64 definition says the same
+            with np.errstate(invalid="ignore", divide="ignore"):
+                ploss, pg = xent.softmax_cross_entropy_test(X, labels)
+            assert np.array_equal(np.isfinite(ploss), np.isfinite(loss)) and ploss[hot] == np.inf
+            assert np.allclose(np.delete(ploss, hot), np.delete(loss, hot), rtol=1e-12, atol=1e-12) and np.allclose(pg, g, rtol=0, atol=1e-14)
+    # a row with no finite logit, with +inf or with NaN is NaN in that row only
+    X = np.array([[0.0, 1.0, 2.0], [-np.inf] * 3, [0.0, np.inf, 1.0], [np.nan, 0.0, 1.0], [1.0, 2.0, 3.0]])
+    loss = ER.xent_ref(X, np.array([0, 1, 2, 1, 2]))[0]
+    with np.errstate(invalid="ignore"):
+        ploss = xent.softmax_cross_entropy_test(X, np.array([0, 1, 2, 1, 2]))[0]
+    for got in (loss, ploss):
+        assert np.isnan(got).tolist() == [False, True, True, True, False]
+
+
+def test_float32_model_of_the_streamed_recurrence():
+    """A float32 NumPy model of xent_long_kernel (per-lane running maximum, rescale, merge of the 1024 lanes) on the masked inputs, on both
+    access widths: it agrees with float64 at the fp32 loss bars -- and without the rule that a -inf logit adds nothing it is NaN on the
+    rows head, unit0 and single, so the model can tell the two recurrences apart."""
+    import _parity as P
+    hot = ER.MASKED_LABEL_ROW
+    for K, V, nan_rows in ((16385, 1, ("head", "unit0", "single")), (32776, 8, ("head", "unit0"))):
+        X, labels = ER.xent_masked_inputs(K, "f32")
+        want = ER.xent_ref(X, labels)[0]
+        got = ER.xent_long_model_f32(X, labels, V)
+        assert got.dtype == np.float32 and got[hot] == np.inf
+        l2, mx = P.errors(np.delete(got, hot), np.delete(want, hot))
+        print("K %d V %d: model loss L2 %.2e max %.2e" % (K, V, l2, mx))
+        assert l2 <= P.L2_BAR["f32"] and mx <= P.MAX_BAR["f32"], (K, V, l2, mx)
+        before = ER.xent_long_model_f32(X, labels, V, skip_masked=False)
+        for name in nan_rows:
+            assert np.isnan(before[ER.MASKS.index(name)]), (K, V, name, before)
+        assert before[ER.MASKS.index("tail")] == got[ER.MASKS.index("tail")]       # the control: masked classes behind finite ones
+    # finite rows: the rule changes no bit
+    X, labels, _ = ER.xent_inputs(2, 16385, "f32", "uniform")
+    assert np.array_equal(ER.xent_long_model_f32(X, labels, 1), ER.xent_long_model_f32(X, labels, 1, skip_masked=False))
+    assert P.errors(ER.xent_long_model_f32(X, labels, 1), ER.xent_ref(X, labels)[0])[0] <= P.L2_BAR["f32"]

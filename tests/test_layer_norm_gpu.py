@@ -268,3 +268,81 @@ def test_captured_forward_and_backward_replay_onto_refreshed_inputs(env, axis):
     c2 = make_case(K, N, axis, S, "bf16", relu=False, seed=4242)
     l2, _ = P.errors(P.to_host(got[1]), c2["MEAN"])
     assert l2 <= P.L2_BAR["f32"]
+
+
+OUTLIER_PARAMS = [(case, dtype) for case in LR.OUTLIER_CASES for dtype in LR.outlier_dtypes(case)]
+
+
+def check_outlier(name, got, c, dtype, ctx):
+    """An fp32 result: max(the fp32 bar, 8 x the error of the float32 NumPy model on the same input), for the L2 and the max figure alike
+    (the margin is over the model, whose pairwise sums a lane-serial kernel does not reproduce -- not over the code under test).  A 16-bit
+    result: the bars of its dtype against float64 rounded once, as everywhere in this file."""
+    got = P.to_host(got)
+    assert got.shape == c[name].shape and np.isfinite(got).all(), (ctx, name)
+    if dtype != "f32":
+        l2, mx = P.errors(got, orc.round_to(c[name], dtype))
+        print(ctx, name, "device l2 %.3g max %.3g" % (l2, mx))
+        assert l2 <= P.L2_BAR[dtype] and mx <= P.MAX_BAR[dtype], (ctx, name, l2, mx)
+        return
+    l2_bar, mx_bar, ml2, mmx = LR.outlier_bars(c, name, P.L2_BAR["f32"], P.MAX_BAR["f32"])
+    l2, mx = P.errors(got, c[name])
+    print(ctx, name, "model l2 %.3g max %.3g | device l2 %.3g max %.3g | bars %.3g %.3g" % (ml2, mmx, l2, mx, l2_bar, mx_bar))
+    assert l2 <= l2_bar and mx <= mx_bar, (ctx, name, l2, mx, l2_bar, mx_bar)
+
+
+OUTLIER_MARKS = [pytest.mark.parametrize("at", (0, 1), ids=("first-feature", "second-feature")),
+                 pytest.mark.parametrize("A", LR.OUTLIER_SIZES, ids=lambda a: "A%d" % a),
+                 pytest.mark.parametrize("case,dtype", OUTLIER_PARAMS, ids=["K%d-N%d-a%d-S%d-%s" % (c + (d,)) for c, d in OUTLIER_PARAMS])]
+
+
+def outlier_marks(fn):
+    for m in reversed(OUTLIER_MARKS):
+        fn = m(fn)
+    return fn
+
+
+@outlier_marks
+def test_outlier_first_feature_keeps_the_variance(env, case, dtype, A, at):
+    """N(0, 1) inputs whose first feature of every segment is +A / -A (a massive-activation dimension), and as the control the same
+    outlier in the second feature: the statistics may not depend on which element a kernel reads first.  mean, rstd (fp32 in every dtype)
+    and an fp32 y against float64 by check_outlier, a 16-bit y at the bars of its dtype.
+    With var = sum (x - c)^2 / Ks - (mean - c)^2, c = the first feature, the kernels of the axis-0 statistics and of the streamed axis-1
+    row missed the rstd bar on every first-feature case and met it on every control.  Measured rstd L2 error of that form on an MI355X,
+    next to the float32 model of tests/_layer_norm_ref.py (stats_f32_shifted): Ks = 512: 1.1e-5 (model 1.4e-5) at A = 30, 1.7e-5 (2.1e-5)
+    at A = 1000; Ks = 8200 on axis 0: 6.9e-5 (1.4e-4) and 8.1e-4 (1.2e-3), bf16 8.6e-4; Ks = 8193 on axis 1: 1.5e-5 (4.9e-5) and 8.7e-5
+    (9.0e-4).  The segments of 48 features failed on the max figure of y only (3.4e-5 against 2.6e-5); their rstd stayed under 2e-6.
+    The two-pass kernels measure at most 2.0e-7 over all cases (the float32 two-pass model, whose NumPy sum down a column is serial: up
+    to 3.4e-6 at Ks = 8200 on axis 0, which is where the model's half of the bar comes into play)."""
+    torch, norms = env
+    K, N, axis, S = case
+    c = LR.outlier_case(K, N, axis, S, dtype, A, at)
+    ctx = (case, dtype, A, at)
+    x, dy, g, b = dev(torch, c, dtype)
+    y, mean, rstd = norms.layer_norm_fwd(x, g, b, axis=axis, segments=S)
+    assert tuple(mean.shape) == c["MEAN"].shape == tuple(rstd.shape) and mean.dtype == rstd.dtype == torch.float32
+    check_outlier("MEAN", mean, c, "f32", ctx)
+    check_outlier("RSTD", rstd, c, "f32", ctx)
+    check_outlier("Y", y, c, dtype, ctx)
+
+
+@outlier_marks
+def test_outlier_feature_backward_from_float64_statistics(env, case, dtype, A, at):
+    """The backward on the same inputs, from the float64 statistics rounded to fp32, so that it stands apart from the forward: dx, dg and
+    db by check_outlier against the float32 NumPy evaluation of the formulas of include/bsmm_norm.h.
+    The max figure is max |diff| / mean |dg|, and the outlier's own dg is 470 times the mean |dg| (57.7 against 0.122 at K8193 bf16):
+    there 2e-5 of the mean is 0.64 of ONE fp32 step of the value, so the bar asks for a dg that is all but correctly rounded.  With the
+    term dy (x - mean) rstd and its sum over the samples in fp32 the kernels missed the max figure of dg on two cases, 0.9 steps from float64:
+      K8193-N3-a1-S1-bf16-A1000-first-feature:   device 2.84e-5, bar max(2e-5, 8 x 2.81e-6) = 2.25e-5
+      K8200-N8-a0-S1-f16-A1000-second-feature:   device 6.20e-5, bar max(2e-5, 8 x 6.93e-6) = 5.54e-5
+    The axis-0 kernel and the column walk of the streamed axis-1 row now form that term and sum it in fp64 within a partial: 2.81e-6 and
+    6.93e-6 on an MI355X, the model's own figures (both are the correctly rounded fp32 value); over all 52 cases dg is at most 0.13 of its bar."""
+    torch, norms = env
+    K, N, axis, S = case
+    c = LR.outlier_case(K, N, axis, S, dtype, A, at)
+    ctx = (case, dtype, A, at)
+    x, dy, g, b = dev(torch, c, dtype)
+    m32, r32 = (torch.from_numpy(np.ascontiguousarray(c[n])).to("cuda") for n in ("MEAN32", "RSTD32"))
+    dx, dg, db = norms.layer_norm_bwd(dy, x, g, b, m32, r32, axis=axis, segments=S)
+    check_outlier("DX", dx, c, dtype, ctx)
+    check_outlier("DG", dg, c, "f32", ctx)
+    check_outlier("DB", db, c, "f32", ctx)
