@@ -86,7 +86,7 @@ gather8_kernel(const float* __restrict__ S32, const int32_t* __restrict__ plan, 
     *reinterpret_cast<uint2*>(dst) = r;
 }
 
-// fp32 form (round 4: the fp32 weight gradient of bsize 8 through the bf16 streaming kernel, bsmm_api.hip::updat8_f32_split): the same gather,
+// fp32 form (round 4: the fp32 weight gradient of bsize 8 through the bf16 streaming kernel, bsmm_updat_dispatch.h::updat8_f32_split): the same gather,
 // DW8 in fp32 (no rounding)
 __global__ void __launch_bounds__(256)
 gather8_f32_kernel(const float* __restrict__ S32, const int32_t* __restrict__ plan, float* __restrict__ DW8, float alpha, float beta,

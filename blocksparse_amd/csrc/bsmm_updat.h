@@ -29,7 +29,7 @@ __global__ void __launch_bounds__(256)
 updat32_kernel(PtrList8 Xs, PtrList8 Es, typename DT::T* __restrict__ DW, const int32_t* __restrict__ lut,
                int blocks, int N, int Cf, int Kf, int pcount, float alpha, float beta, const float* __restrict__ gate = nullptr,
                const int32_t* __restrict__ only_if = nullptr) {
-    if (only_if && only_if[0] == 0) return;          // repair pass of the fp32 bf16-split paths (bsmm_api.hip): runs only when their flag is set
+    if (only_if && only_if[0] == 0) return;          // repair pass of the fp32 bf16-split paths (bsmm_updat_dispatch.h): runs only when their flag is set
     typedef typename DT::T T;
     __shared__ float red[4 * 1024];
     const int w = updat_block(blockIdx.x, blocks);
@@ -79,7 +79,7 @@ __global__ void __launch_bounds__(256)
 updat16_kernel(PtrList8 Xs, PtrList8 Es, typename DT::T* __restrict__ DW, const int32_t* __restrict__ lut,
                int blocks, int N, int Cf, int Kf, int pcount, float alpha, float beta, const float* __restrict__ gate = nullptr,
                const int32_t* __restrict__ only_if = nullptr) {
-    if (only_if && only_if[0] == 0) return;          // repair pass of the fp32 bf16-split paths (bsmm_api.hip): runs only when their flag is set
+    if (only_if && only_if[0] == 0) return;          // repair pass of the fp32 bf16-split paths (bsmm_updat_dispatch.h): runs only when their flag is set
     typedef typename DT::T T;
     constexpr int KS = Frag16<DT>::KS;   // n per MFMA slab: 32 (16-bit) / 16 (f32)
     constexpr int KL = Frag16<DT>::KL;   // n per lane per slab: 8 / 4
@@ -138,7 +138,7 @@ __global__ void __launch_bounds__(256)
 updat_valu_kernel(PtrList8 Xs, PtrList8 Es, typename DT::T* __restrict__ DW, const int32_t* __restrict__ lut,
                   int blocks, int N, int Cf, int Kf, int pcount, float alpha, float beta, const float* __restrict__ gate = nullptr,
                const int32_t* __restrict__ only_if = nullptr) {
-    if (only_if && only_if[0] == 0) return;          // repair pass of the fp32 bf16-split paths (bsmm_api.hip): runs only when their flag is set
+    if (only_if && only_if[0] == 0) return;          // repair pass of the fp32 bf16-split paths (bsmm_updat_dispatch.h): runs only when their flag is set
     typedef typename DT::T T;
     constexpr int CH = 64;
     constexpr int OUTS = BS * BS;

@@ -289,7 +289,7 @@ updat16_rows_kernel(PtrList8 Xs, PtrList8 Es, typename DT::T* __restrict__ DW, f
 }
 
 // DW = alpha * [gate *] (sum over the parts' images) + beta * DW, rounded once (fp32 DW: the fp32 call through six bf16 piece pairs,
-// bsmm_api.hip::updat16_f32_rows -- skip_if is its non-finite flag: the repair pass writes DW then)
+// bsmm_updat_dispatch.h::updat16_f32_rows -- skip_if is its non-finite flag: the repair pass writes DW then)
 template <class DT>
 __global__ void __launch_bounds__(256)
 updat16_rows_finalize_kernel(const float* __restrict__ scratch, typename DT::T* __restrict__ DW, size_t nel, int split, float alpha, float beta,

@@ -139,7 +139,7 @@ template <class DT>
 __global__ void __launch_bounds__(256, 4)
 updat32_a1_small_kernel(PtrList8 Xs, PtrList8 Es, typename DT::T* __restrict__ DW, const int32_t* __restrict__ lut,
                         int blocks, int N, int Cf, int Kf, int pcount, float alpha, float beta, const float* __restrict__ gate, int q64 = 0) {
-    // (q64, round 6: the blocks are the quadrants of 64 x 64 blocks, 4 w64 + 2 (row half) + (column half), bsmm_api.hip::updat64 -- every element goes
+    // (q64, round 6: the blocks are the quadrants of 64 x 64 blocks, 4 w64 + 2 (row half) + (column half), bsmm_updat_dispatch.h::updat64 -- every element goes
     //  to its place in the 64 x 64 block and the gate is the 64-block's, as in updat2_reduce_kernel: short minibatches at bsize 64 ran the streaming
     //  kernel before, 35 us at N = 64 where this one takes 6)
     typedef typename DT::T T;

@@ -733,7 +733,7 @@ updat2_reduce_kernel(const float* __restrict__ parts, typename DT::T* __restrict
         const int q = qq + 2 * hq;
         const float4 acc = hq ? acc1 : acc0;
         const float r[4] = {acc.x, acc.y, acc.z, acc.w};
-        // (q64: the blocks are the quadrants of 64 x 64 blocks, 4 w64 + 2 (row half) + (column half), bsmm_api.hip::updat64 -- the element goes to
+        // (q64: the blocks are the quadrants of 64 x 64 blocks, 4 w64 + 2 (row half) + (column half), bsmm_updat_dispatch.h::updat64 -- the element goes to
         //  its place in the 64 x 64 block, the gate is the 64-block's: no separate pass puts the quadrants together)
         const int row = 8 * q + 4 * (l >> 5), col = l & 31;
         const size_t o = q64 ? (size_t)(w >> 2) * 4096 + (size_t)(32 * ((w >> 1) & 1) + row) * 64 + 32 * (w & 1) + col : (size_t)w * 1024 + (size_t)row * 32 + col;

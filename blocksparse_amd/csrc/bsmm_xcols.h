@@ -30,7 +30,7 @@ namespace bsmm {
 // constants live in vector registers across the loop).  tests/test_codeobj.py now fails on any spill of a hot kernel.
 // A non-finite x leaves NaN pieces (Inf: 0x7f7f, Inf, NaN; NaN: NaN all the way), so every output that x enters is NaN -- non-finite
 // exactly where the unsplit IEEE product is non-finite (Inf or NaN there).  The weight-gradient paths do better: split3_x_kernel raises a
-// flag for such inputs and the call is re-run on the fp32 kernels (bsmm_api.hip::f32_split_repair), which reproduces IEEE's Inf / NaN sets.
+// flag for such inputs and the call is re-run on the fp32 kernels (bsmm_updat_dispatch.h::f32_split_repair), which reproduces IEEE's Inf / NaN sets.
 __device__ __forceinline__ void split3(float x, uint32_t& b1, uint32_t& b2, uint32_t& b3) {
     uint16_t p1 = DTbf16::from_f32(x);
     p1 -= (uint16_t)((p1 & 0x7fffu) == 0x7f80u);      // rounded up to Inf (or was Inf): the largest finite bf16 instead

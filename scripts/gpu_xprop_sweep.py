@@ -1,4 +1,4 @@
-"""staged plan kernel (forced) vs per-segment kernel (plan ignored) over the minibatch: data for the cost model in xprop_path"""
+"""staged plan kernel (forced) vs per-segment kernel (plan ignored) over the minibatch: data for the cost model in xprop_route"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))

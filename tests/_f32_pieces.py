@@ -1,5 +1,5 @@
 """Host helpers (NumPy only) for the tests of the fp32 routes that multiply bf16 PIECES: every fp32 x is split into x1 + x2 + x3
-(csrc/bsmm_xcols.h::split3) and x * y is the sum of the six piece products PAIRS below (bsmm_api.hip::f32_split_prologue, the MFMA sequence
+(csrc/bsmm_xcols.h::split3) and x * y is the sum of the six piece products PAIRS below (bsmm_updat_dispatch.h::f32_split_prologue, the MFMA sequence
 of xcol32s_kernel / xcol32sf_kernel).  Here: the split restated bit for bit, inputs that HAVE a third piece, selector partners that isolate
 single pairs, the product with any pair list (the true one and its mutants), an fp32 noise model, and the bar between the two.
 

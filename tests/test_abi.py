@@ -204,6 +204,47 @@ def test_argument_validation_without_gpu(lib):
     assert L.bsmm_gate_weights(one, one, one, 4, 32, lib.BF16, 3, None) == -2
 
 
+def test_short_workspace_is_refused_before_anything_is_enqueued(lib):
+    """A missing workspace, one 16 bytes short of bsmm_workspace_bytes() and one that is not 16-byte aligned are refused with
+    BSMM_ERR_WORKSPACE by the ONE check of the call's route, before a pre-pass or a kernel is enqueued (the operand addresses are fakes).
+    The routes are pinned by flags, so no cost model enters: (a) per-segment fprop -- the transposed copy of W; (b) per-segment and (c) V_FMA
+    bprop over a locked table -- the fp32 accumulators; (d) the fp32 split kernel -- the weight pieces.  No case combines fprop and locks."""
+    import _parity as P
+    from blocksparse_amd import lut as LT
+    from blocksparse_amd.matmul import _host_plan
+    L = lib.load()
+    one = ctypes.c_void_p(256)
+    lay = P.ba_layout(40, 3, seed=1)
+    plain, locked = LT.build_tables(lay, segmented=False), LT.build_tables(lay, segmented=True)
+    assert plain["fprop"]["locks"] == 0 and locked["bprop"]["locks"] > 0
+
+    def args(t, op, bs, dt, flags):
+        side = t["fprop"] if op == lib.OP_FPROP else t["bprop"]
+        a = lib.BsmmArgs()
+        a.lut = 4096
+        a.blocks, a.bsize, a.dtype, a.N, a.axis, a.flags = t["blocks"], bs, dt, 64, 1, flags
+        a.segments, a.locks, a.shared = side["segments"], side["locks"], side["shared"]
+        a.C, a.K = (t["CB"] * bs, t["KB"] * bs) if op == lib.OP_FPROP else (t["KB"] * bs, t["CB"] * bs)
+        return a
+    cases = [("a32", args(plain, lib.OP_FPROP, 32, lib.BF16, lib.FLAG_NO_PLAN), lib.OP_FPROP, plain["blocks"] * 1024 * 2),
+             ("a16", args(plain, lib.OP_FPROP, 16, lib.BF16, lib.FLAG_NO_PLAN), lib.OP_FPROP, plain["blocks"] * 256 * 2),
+             ("b", args(locked, lib.OP_BPROP, 32, lib.BF16, lib.FLAG_NO_PLAN), lib.OP_BPROP, 64 * locked["CB"] * 32 * 4),
+             ("c", args(locked, lib.OP_BPROP, 32, lib.BF16, lib.FLAG_FORCE_VALU), lib.OP_BPROP, 64 * locked["CB"] * 32 * 4)]
+    d = args(plain, lib.OP_FPROP, 32, lib.F32, lib.FLAG_FORCE_PLAN)
+    f = plain["fprop"]
+    words = _host_plan(f["lut"], f["segments"], plain["blocks"], plain["KB"], 32, lib.F32, 1)
+    assert L.bsmm_plan_attach(ctypes.byref(d), words.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), words.size, ctypes.c_void_p(4096)) == 0
+    assert d.plan_magic == 0x42535843 and d.C % 32 == 0
+    cases.append(("d", d, lib.OP_FPROP, 6 * plain["blocks"] * 1024))
+    for name, a, op, want in cases:
+        need = L.bsmm_workspace_bytes(op, ctypes.byref(a))
+        assert need == want and need % 16 == 0, (name, need, want)
+        call = L.bsmm_fprop if op == lib.OP_FPROP else L.bsmm_bprop
+        for ws, nbytes in ((None, need), (1 << 20, need - 16), ((1 << 20) + 8, need + 64)):
+            a.workspace, a.workspace_bytes = ws, nbytes
+            assert call(one, one, one, ctypes.byref(a)) == -3, (name, ws, nbytes)
+
+
 def _check_xcol_plan(plan, f, t, n_out):
     """xcol plan (build_xcol_plan): per group the union of input PAIRS (possibly rotated), per wave / half / step a weight id or -1."""
     assert plan[0] == 0x42535843 and plan[8] == n_out
@@ -809,9 +850,10 @@ def test_plan_attach_descriptor_and_host_side_rejection(lib):
 
 def test_library_reads_no_environment_and_keeps_no_switches(lib):
     """include/bsmm.h promises a stateless library: no getenv, no process-wide kernel switch in the sources."""
-    src = ""
-    for f in ("bsmm_api.hip", "bst_api.hip", "bsmm_dist.hip"):
-        src += open(os.path.join(ROOT, "blocksparse_amd", "csrc", f)).read()
+    csrc = os.path.join(ROOT, "blocksparse_amd", "csrc")
+    files = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".h")))
+    assert {"bsmm_api.hip", "bsmm_dispatch.h", "bsmm_xprop_dispatch.h", "bsmm_updat_dispatch.h", "bst_api.hip", "bsmm_dist.hip"} <= set(files)
+    src = "".join(open(os.path.join(csrc, f)).read() for f in files)
     assert "getenv" not in src and "g_variant" not in src and "static bool attr_set" not in src
     assert not hasattr(ctypes.CDLL(lib.LIB_PATH), "bsmm_set_kernel_variant")
 

@@ -3,7 +3,7 @@ test_f32_pieces_host.py, shows that the suite's usual fp32 inputs have none and 
 
   xprop  K_XCOL32_F32SPLIT: feature axis 1 with the split fused into the kernel, feature axis 0 with the pre-split pass (both through the C ABI
          with prepared_w = NULL: the library splits W too), feature axis 1 with the pieces of bsmm_prepare_weights (the product API);
-  updat  the four routes of bsmm_api.hip::f32_split_route -- K_UPDAT_STREAM (bsize 32), K_UPDAT_SUPER8 (bsize 8, both axes),
+  updat  the four routes of bsmm_updat_dispatch.h::f32_split_route -- K_UPDAT_STREAM (bsize 32), K_UPDAT_SUPER8 (bsize 8, both axes),
          K_UPDAT16_WIN (bsize 16, axis 1), K_UPDAT16_ROWS (bsize 16, axis 0).
 
 Three kinds of check, every one with the plan forced (set_kernel_variant(3)) and the kernel family asserted:

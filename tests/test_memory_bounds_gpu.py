@@ -16,7 +16,7 @@ thresholds (XSN_NMAX / 8, / 2 and XSN_NMAX itself, BSMM_SMALL_N_MAX, UTS_NMAX, U
 feature axis 0, grids of 37 x 53, 1 x 70, 70 x 1, 5 x 5 dense, one block, an empty row and column of blocks, operands offset by one element.
 (BlocksparseMatMul.LONG_MINIBATCH needs a grid of 64 windows of 32 x 32 blocks -- 256 blocks a side -- and is not reachable at these sizes.)
 Production dispatch where it reaches a family at such a shape, the suite's usual switches (set_kernel_variant, plan_options) elsewhere; the
-expected code of a production case is what the dispatch rules of csrc/bsmm_api.hip give for it on 256 compute units.  A retuned dispatch
+expected code of a production case is what the dispatch rules of csrc/bsmm_xprop_dispatch.h and csrc/bsmm_updat_dispatch.h give for it on 256 compute units.  A retuned dispatch
 constant therefore turns (a) red for the cases it moves: read the rule, and where the new choice is the intended one put its code into the row --
 or move the case's shape so that the family it is there for is still reached (test_memory_bounds_table.py says which must be).
 
@@ -31,7 +31,7 @@ import _guard as GD
 import _parity as P
 from oracle import bsmm_oracle as orc
 
-# what the shapes below straddle (the dispatch thresholds of csrc/bsmm_api.hip; test_memory_bounds_table.py checks them against the source)
+# what the shapes below straddle (the dispatch thresholds of csrc/bsmm_xprop_dispatch.h and csrc/bsmm_updat_dispatch.h; test_memory_bounds_table.py checks them against the source)
 XS0_NMAX, XSN_NMAX, UAW_NMAX, UTS_NMAX, SMALL_N_MAX = 512, 512, 128, 768, 4096
 
 Case = collections.namedtuple("Case", "id bs axis dt lay N variant opts flow seg exp pairs alpha beta mis gate split mode")

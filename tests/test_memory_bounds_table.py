@@ -1,5 +1,5 @@
 """CPU tier: the case table of tests/test_memory_bounds_gpu.py against the trace codes of blocksparse_amd/_lib.py and the dispatch thresholds
-of csrc/bsmm_api.hip.  A kernel family (or trace variant) added to the library must get a case in the memory-contract tier, or this fails."""
+of csrc/bsmm_xprop_dispatch.h and csrc/bsmm_updat_dispatch.h.  A kernel family (or trace variant) added to the library must get a case in the memory-contract tier, or this fails."""
 import os
 import re
 
@@ -60,7 +60,7 @@ def test_table_is_explicit_and_stable():
         assert {"bf16", "f16"} <= fam_types[fam], (fam, fam_types[fam])
     for fam in ("K_XCOL32_F32SPLIT", "K_XPROP_SEGMENT", "K_XPROP_VALU", "K_UPDAT_VALU", "K_UPDAT_STREAM", "K_UPDAT16_WIN", "K_UPDAT16_ROWS", "K_UPDAT_SUPER8", "K_UPDAT_BLOCK"):
         assert "f32" in fam_types[fam], fam
-    # the five small-minibatch kernels of xprop_typed: the narrow one (bsize 8 and 16 on feature axis 1), bsize 8 / 16 / 32 on feature axis 0, bsize 32 on axis 1
+    # the five small-minibatch kernels of launch_xsmall: the narrow one (bsize 8 and 16 on feature axis 1), bsize 8 / 16 / 32 on feature axis 0, bsize 32 on axis 1
     small = {(c.bs, c.axis) for c in T.CASES if c.exp[0] == "K_XPROP_SMALL" and c.exp[1] == "K_XPROP_SMALL"}
     assert small >= {(8, 1), (16, 1), (8, 0), (16, 0), (32, 0), (32, 1)}, small
     # the streaming weight gradient with and without direct blocks, the raw-sums form, the fp32 split routes of bsize 8 / 16 / 32, bsize 64, both gate routes
@@ -75,9 +75,9 @@ def test_table_is_explicit_and_stable():
 
 
 def test_thresholds_match_the_source():
-    with open(os.path.join(CSRC, "bsmm_api.hip")) as f:
-        src = f.read()
-    for name, val in (("XS0_NMAX", T.XS0_NMAX), ("XSN_NMAX", T.XSN_NMAX), ("UAW_NMAX", T.UAW_NMAX), ("UTS_NMAX", T.UTS_NMAX), ("BSMM_SMALL_N_MAX", T.SMALL_N_MAX)):
+    xsrc, usrc = (open(os.path.join(CSRC, fn)).read() for fn in ("bsmm_xprop_dispatch.h", "bsmm_updat_dispatch.h"))
+    for name, val, src in (("XS0_NMAX", T.XS0_NMAX, xsrc), ("XSN_NMAX", T.XSN_NMAX, xsrc), ("UAW_NMAX", T.UAW_NMAX, usrc), ("UTS_NMAX", T.UTS_NMAX, usrc),
+                           ("BSMM_SMALL_N_MAX", T.SMALL_N_MAX, xsrc)):
         m = re.search(r"#define %s (\d+)" % name, src)
         assert m and int(m.group(1)) == val, (name, m and m.group(1), val)
     ns = {(c.bs, c.axis): set() for c in T.CASES}

@@ -140,7 +140,7 @@ def test_small_minibatch_updat_bsize64(env):
 def test_small_minibatch_axis0_fuzz(env):
     """Eighteen seeded random cases over the small-minibatch kernels of feature axis 0: layouts of 1 .. 60 blocks a side at 3 .. 100 %, block sizes
     8 / 16 / 32, minibatches that are multiples of 8 up to 1024, bf16 / fp16 -- all three passes against the float64 oracle (the kernel family of
-    fprop asserted where the rule of bsmm_api.hip must take the small kernel: N <= 512)."""
+    fprop asserted where the rule of bsmm_xprop_dispatch.h must take the small kernel: N <= 512)."""
     torch, BSMM, lib = env
     rng = np.random.default_rng(20260930)
     for it in range(18):
