@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get("BSMM_LIB") or os.path.join(_HERE, "libbsmm_hip.so")
 
 ABI_VERSION = 128        # include/bsmm.h BSMM_VERSION this binding was written against (struct layout, plan formats, option bits)
 F32, F16, BF16 = 0, 1, 2
+ERR_UNSUPPORTED = -2     # BSMM_ERR_UNSUPPORTED: the one return code callers act on (they take another route); every other one is raised
 OP_FPROP, OP_BPROP, OP_UPDAT = 0, 1, 2
 FLAG_GATED_DW, FLAG_FORCE_VALU, FLAG_NO_PLAN, FLAG_FORCE_PLAN, FLAG_DW_SUMS, FLAG_FORCE_MID = 1, 2, 4, 8, 16, 32
 # bsmm_args.trace codes (include/bsmm.h BSMM_K_*)
@@ -395,6 +396,14 @@ def dtype_code(dtype):
     """The BSMM_F32 / BSMM_F16 / BSMM_BF16 code of a torch dtype, None for any other dtype: each caller raises its own error."""
     import torch
     return {torch.float32: F32, torch.float16: F16, torch.bfloat16: BF16}.get(dtype)
+
+
+def require_dtype_code(dtype, error=None):
+    """``dtype_code`` for callers that take nothing else: raises ``error(dtype)`` (default: the operator classes' TypeError)."""
+    code = dtype_code(dtype)
+    if code is None:
+        raise error(dtype) if error is not None else TypeError("blocksparse_amd: unsupported dtype %s (float32, float16, bfloat16)" % dtype)
+    return code
 
 
 def error_string(code):

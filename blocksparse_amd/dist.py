@@ -67,13 +67,12 @@ class RcclComm(object):
         h = ctypes.c_void_p()
         _lib.check(self._lib.bsmm_dist_create(ctypes.byref(h), ident, self.rank, self.world, self.device.index or 0), "bsmm_dist_create")
         self._h = h
-        self._check = _lib.check
+        self._check, self._dtype_code = _lib.check, _lib.require_dtype_code
 
     def begin(self, t):
         """in-place all-reduce(sum) of a contiguous CUDA tensor, ordered after the work enqueued so far on the current stream"""
-        from .matmul import _dtype_code
         st = torch.cuda.current_stream(t.device).cuda_stream
-        self._check(self._lib.bsmm_dist_allreduce_begin(self._h, t.data_ptr(), t.numel(), _dtype_code(t.dtype), st), "bsmm_dist_allreduce_begin")
+        self._check(self._lib.bsmm_dist_allreduce_begin(self._h, t.data_ptr(), t.numel(), self._dtype_code(t.dtype), st), "bsmm_dist_allreduce_begin")
 
     def end(self):
         """make the current stream wait for the collective"""
@@ -88,10 +87,9 @@ class RcclComm(object):
         shard, all-gather of the finished shards into ``dw`` -- all on the handle's stream, ordered after the current stream.
         ``sums`` must have room for world * shard floats behind its first element (the library checks the capacity we declare:
         what the tensor's storage really holds)."""
-        from .matmul import _dtype_code
         st = torch.cuda.current_stream(dw.device).cuda_stream
         self._check(self._lib.bsmm_dist_dw_begin(self._h, sums.data_ptr(), sums_capacity(sums), dw.data_ptr(), staging.data_ptr(),
-                                                 gate.data_ptr() if gate is not None else None, blocks, bsize, _dtype_code(dw.dtype),
+                                                 gate.data_ptr() if gate is not None else None, blocks, bsize, self._dtype_code(dw.dtype),
                                                  alpha, beta, st), "bsmm_dist_dw_begin")
 
     def close(self):

@@ -47,46 +47,33 @@ def _capturing():
         return False
 
 
-def _dtype_code(dt):
-    if dt == torch.float32:
-        return _lib.F32
-    if dt == torch.float16:
-        return _lib.F16
-    if dt == torch.bfloat16:
-        return _lib.BF16
-    raise TypeError("blocksparse_amd: unsupported dtype %s (float32, float16, bfloat16)" % dt)
+_dtype_code = _lib.require_dtype_code
+
+
+def _build_plan(family, lut, *args):
+    """The host words of one schedule of the library: ask bsmm_<family>_plan_words for the size, allocate, let bsmm_<family>_plan_build
+    fill them.  None where the library has no plan kernel for the configuration."""
+    lib = _lib.load()
+    lut = np.ascontiguousarray(lut, dtype=np.int32)
+    ip = ctypes.POINTER(ctypes.c_int32)
+    words = getattr(lib, "bsmm_%s_plan_words" % family)(lut.ctypes.data_as(ip), *args)
+    if words < 0:
+        raise RuntimeError("bsmm_%s_plan_words rejected the lookup table" % family)
+    if words == 0:
+        return None
+    out = np.empty(words, dtype=np.int32)
+    _lib.check(getattr(lib, "bsmm_%s_plan_build" % family)(lut.ctypes.data_as(ip), *args, out.ctypes.data_as(ip)), "bsmm_%s_plan_build" % family)
+    return out
 
 
 def _host_plan(lut, segments, blocks, n_out_blocks, bsize, dtype_code, axis, options=0):
     """Grouped-kernel schedule for one xprop lut (host call into the library: bsmm_xprop_plan_build)."""
-    lib = _lib.load()
-    lut = np.ascontiguousarray(lut, dtype=np.int32)
-    ip = ctypes.POINTER(ctypes.c_int32)
-    words = lib.bsmm_xprop_plan_words(lut.ctypes.data_as(ip), segments, blocks, n_out_blocks, bsize, dtype_code, axis, options)
-    if words < 0:
-        raise RuntimeError("bsmm_xprop_plan_words rejected the lookup table")
-    if words == 0:
-        return None
-    out = np.empty(words, dtype=np.int32)
-    _lib.check(lib.bsmm_xprop_plan_build(lut.ctypes.data_as(ip), segments, blocks, n_out_blocks, bsize, dtype_code, axis, options,
-                                         out.ctypes.data_as(ip)), "bsmm_xprop_plan_build")
-    return out
+    return _build_plan("xprop", lut, segments, blocks, n_out_blocks, bsize, dtype_code, axis, options)
 
 
 def _host_updat_plan(updat_lut, blocks, CB, KB, bsize, dtype_code, axis, options=0):
     """Work items of the windowed updat kernel (host call into the library: bsmm_updat_plan_build)."""
-    lib = _lib.load()
-    lut = np.ascontiguousarray(updat_lut, dtype=np.int32)
-    ip = ctypes.POINTER(ctypes.c_int32)
-    words = lib.bsmm_updat_plan_words(lut.ctypes.data_as(ip), blocks, CB, KB, bsize, dtype_code, axis, options)
-    if words < 0:
-        raise RuntimeError("bsmm_updat_plan_words rejected the lookup table")
-    if words == 0:
-        return None
-    out = np.empty(words, dtype=np.int32)
-    _lib.check(lib.bsmm_updat_plan_build(lut.ctypes.data_as(ip), blocks, CB, KB, bsize, dtype_code, axis, options,
-                                         out.ctypes.data_as(ip)), "bsmm_updat_plan_build")
-    return out
+    return _build_plan("updat", updat_lut, blocks, CB, KB, bsize, dtype_code, axis, options)
 
 
 class _Plan(object):
@@ -113,35 +100,38 @@ class _DeviceTables(object):
 
         def plan(words):
             return _Plan(words, device) if words is not None else None
+
+        def xprop_plans(dtype_code, options):      # (fprop, bprop): the two passes' plans of one kind
+            return tuple(plan(_host_plan(side["lut"], side["segments"], B, n_out, bsize, dtype_code, axis, options))
+                         for side, n_out in ((tables["fprop"], KB), (tables["bprop"], CB)))
+
+        def updat_plan(options):
+            return plan(_host_updat_plan(tables["updat_lut"], B, CB, KB, bsize, _lib.BF16, axis, options))
+
         self.fprop = up(tables["fprop"]["lut"])
         self.bprop = up(tables["bprop"]["lut"])
         self.updat = up(tables["updat_lut"])
         CB, KB, B = tables["CB"], tables["KB"], tables["blocks"]
-        f, b = tables["fprop"], tables["bprop"]
         # plans exist only for 16-bit types (they do not depend on which of the two) ...
-        self.fprop_plan = plan(_host_plan(f["lut"], f["segments"], B, KB, bsize, _lib.BF16, axis, plan_options))
-        self.bprop_plan = plan(_host_plan(b["lut"], b["segments"], B, CB, bsize, _lib.BF16, axis, plan_options))
+        self.fprop_plan, self.bprop_plan = xprop_plans(_lib.BF16, plan_options)
         # bsize 32 on feature axis 1: the barrier-free persistent kernel ('BSX4' plans, csrc/bsmm_xflow.h) for ungated calls; the staged
         # kernel's plans above stay for gated calls and as the comparison path (BlocksparseMatMul.flow = False).  A caller who names
         # another kernel family in plan_options gets exactly that.
         self.fprop_flow = self.bprop_flow = None
         # (bsize 64 runs on the bsize-32 kernels: its composite plan nests whichever bsize-32 plan the options name)
         if bsize in (32, 64) and axis == 1 and not (plan_options & (_lib.PLAN_XCOL_UNSTAGED | _lib.PLAN_XCOL_NARROW | _lib.PLAN_XCOL_FLOW | (7 << _lib.PLAN_XPROP_PH_SHIFT))):
-            self.fprop_flow = plan(_host_plan(f["lut"], f["segments"], B, KB, bsize, _lib.BF16, axis, plan_options | _lib.PLAN_XCOL_FLOW))
-            self.bprop_flow = plan(_host_plan(b["lut"], b["segments"], B, CB, bsize, _lib.BF16, axis, plan_options | _lib.PLAN_XCOL_FLOW))
+            self.fprop_flow, self.bprop_flow = xprop_plans(_lib.BF16, plan_options | _lib.PLAN_XCOL_FLOW)
         self.fprop_plan_f32 = self.bprop_plan_f32 = self.updat_plan = self.updat_plan_long = None
         if xprop_only:        # the doubled tables of gated calls (lut.double_tables): 16-bit fprop / bprop only
             return
         # ... and fp32 has its own (xprop-only) plan kernels for bsize 32; the schedule format is the library's business
-        self.fprop_plan_f32 = plan(_host_plan(f["lut"], f["segments"], B, KB, bsize, _lib.F32, axis, plan_options))
-        self.bprop_plan_f32 = plan(_host_plan(b["lut"], b["segments"], B, CB, bsize, _lib.F32, axis, plan_options))
-        self.updat_plan = plan(_host_updat_plan(tables["updat_lut"], B, CB, KB, bsize, _lib.BF16, axis, plan_options))
+        self.fprop_plan_f32, self.bprop_plan_f32 = xprop_plans(_lib.F32, plan_options)
+        self.updat_plan = updat_plan(plan_options)
         # round 6: 32 x 32-block windows for LONG minibatches on grids of >= 64 such windows at 3.7 .. 5 % density (BASELINE configs[3]: 91 against 100 us at
         # N = 4096; at N <= 2048 the 16 x 16 windows' direct stores win) -- a plan does not know the minibatch, BlocksparseMatMul.updat picks per call
-        self.updat_plan_long = None
         w32 = (-(-CB // 32)) * (-(-KB // 32))
         if bsize == 32 and axis == 1 and not (plan_options & _lib.PLAN_WINDOW_MASK) and w32 >= 64 and 38 * w32 < B <= 52 * w32:
-            self.updat_plan_long = plan(_host_updat_plan(tables["updat_lut"], B, CB, KB, bsize, _lib.BF16, axis, plan_options | _lib.PLAN_STREAM_32))
+            self.updat_plan_long = updat_plan(plan_options | _lib.PLAN_STREAM_32)
 
 
 class BlocksparseMatMul(object):
@@ -163,20 +153,11 @@ class BlocksparseMatMul(object):
             raise ValueError("Unsupported block size with this feature axis")
         layout = np.asarray(layout)
         assert len(layout.shape) == 2
-        self.axis = feature_axis
-        self.bsize = block_size
-        self.z_order = bool(z_order)
-        self.segmented = bool(segmented)
-        self.plan_options = int(plan_options)
-        self.updat_split = int(updat_split)
-        self.name = name if name is not None else "BlocksparseMatMul"
-
         ref = _lut.build_tables(layout, z_order=z_order, segmented=True)      # reference-policy tables
-        self._ref_tables = ref
-        self._dev_tables = ref if segmented else _lut.build_tables(layout, z_order=z_order, segmented=False)
+        dev = ref if segmented else _lut.build_tables(layout, z_order=z_order, segmented=False)
+        self._init_state(dev, ref, block_size, feature_axis, z_order, name if name is not None else "BlocksparseMatMul", segmented,
+                         plan_options, updat_split)
 
-        CB, KB = ref["CB"], ref["KB"]
-        blocks = ref["blocks"]
         self.updat_lut = ref["updat_lut"]
         self.updat_list = [tuple(r) for r in ref["updat_lut"].tolist()]
         f, b = ref["fprop"], ref["bprop"]
@@ -185,17 +166,40 @@ class BlocksparseMatMul(object):
         self.fprop_segments, self.fprop_locks = f["segments"], f["locks"]
         self.bprop_list, self.bprop_lut = b["cols"], b["lut"]
         self.bprop_shared, self.bprop_segments, self.bprop_locks = b["shared"], b["segments"], b["locks"]
+        self.sparsity = round(float(self.blocks) / float(self.CB * self.KB), 3)
+        self.layout = ref["layout"]
+        if block_size == 64:
+            # same weights, cut into 32x32 blocks: inner block n is quadrant (i, j) of outer block b
+            self._inner = BlocksparseMatMul(np.kron(self.layout, np.ones((2, 2), dtype=self.layout.dtype)), block_size=32, feature_axis=feature_axis,
+                                            z_order=z_order, name=self.name + "/32", plan_options=plan_options, updat_split=updat_split)
+            where = {ck: b for b, ck in enumerate(self.updat_list)}
+            self._perm64 = np.array([where[(c // 2, k // 2)] * 4 + (c & 1) * 2 + (k & 1) for c, k in self._inner.updat_list], dtype=np.int64)
+            self._inv64 = np.argsort(self._perm64)
+            self._perm64_dev = {}
 
-        self.flops = blocks * block_size * block_size * 2
+    def _init_state(self, tables, ref_tables, bsize, axis, z_order, name, segmented, plan_options, updat_split, xprop_only=False):
+        """Everything an operator holds besides the public (reference-policy) table attributes: its identity, the tables its device
+        walks with the sizes they imply, and the per-call state -- caches, knobs, sub-operators.  ``__init__`` runs it for a layout's
+        tables, ``_doubled`` for ``lut.double_tables`` of them: an attribute added here exists on both."""
+        self.axis = axis
+        self.bsize = bsize
+        self.z_order = bool(z_order)
+        self.segmented = bool(segmented)
+        self.plan_options = int(plan_options)
+        self.updat_split = int(updat_split)
+        self.name = name
+        self._ref_tables = ref_tables
+        self._dev_tables = tables
+        blocks = tables["blocks"]
+        self.flops = blocks * bsize * bsize * 2
         self.blocks = blocks
-        self.w_shape = (blocks, block_size, block_size)
+        self.w_shape = (blocks, bsize, bsize)
         self.g_shape = (blocks,)
         self.count = 0
-        self.CB, self.KB = CB, KB
-        self.C, self.K = CB * block_size, KB * block_size
-        self.sparsity = round(float(blocks) / float(CB * KB), 3)
-        self.layout = ref["layout"]
+        self.CB, self.KB = tables["CB"], tables["KB"]
+        self.C, self.K = self.CB * bsize, self.KB * bsize
         self._device_cache = {}
+        self._l2_dev = {}
         self._workspaces = {}
         self._args_cache = {}
         self._prepared_w = {}             # op -> (weakref(w), (op, w.data_ptr, w._version, stream), buffer): bsmm_prepare_weights results
@@ -210,15 +214,7 @@ class BlocksparseMatMul(object):
         self.gate_kind = "auto"       # "auto": look at a gate once per (tensor object, version); "binary" / "general": the caller's promise
         self._gate_kind_hit = None
         self._dbl = None
-        self._xprop_only = False
-        if block_size == 64:
-            # same weights, cut into 32x32 blocks: inner block n is quadrant (i, j) of outer block b
-            self._inner = BlocksparseMatMul(np.kron(self.layout, np.ones((2, 2), dtype=self.layout.dtype)), block_size=32, feature_axis=feature_axis,
-                                            z_order=z_order, name=self.name + "/32", plan_options=plan_options, updat_split=updat_split)
-            where = {ck: b for b, ck in enumerate(self.updat_list)}
-            self._perm64 = np.array([where[(c // 2, k // 2)] * 4 + (c & 1) * 2 + (k & 1) for c, k in self._inner.updat_list], dtype=np.int64)
-            self._inv64 = np.argsort(self._perm64)
-            self._perm64_dev = {}
+        self._xprop_only = xprop_only
 
     # ---- bsize 64 on the bsize-32 kernels --------------------------------------------------------
     def _idx64(self, device):
@@ -232,13 +228,23 @@ class BlocksparseMatMul(object):
         return w.contiguous().view(self.blocks, 2, 32, 2, 32).permute(0, 1, 3, 2, 4).reshape(4 * self.blocks, 32, 32).index_select(0, perm)
 
     @staticmethod
-    def _same_weights(entry, w, key):
-        """A cached per-weights image is valid only for the SAME tensor object (weak reference still alive and identical -- a new
-        tensor that the allocator put at the old address is a different object), at the same version, with the same key.
+    def _per_tensor(store, name, t, key, make, use=True):
+        """The one rule for everything cached about a tensor's CONTENTS (prepared pieces, quadrant views, the verdict on a gate): the
+        value ``make(capturing)`` for ``t``, remembered in ``store[name]`` as (weakref(t), key, value).
+        A stored value is valid only for the SAME tensor object (weak reference still alive and identical -- a new tensor that the
+        allocator put at the old address is a different object), at the same version, with the same key.
         Consequence: the cache is PER OBJECT -- pass the parameter itself.  A fresh view of it on every call (``w.detach()``,
         ``w.data``, an AMP cast, a non-contiguous ``w`` that fprop makes contiguous) never hits, and the per-weights preparation (fp32 pieces,
-        bsize-64 quadrant gather) then runs in every fprop / bprop; the results are the same, only slower."""
-        return entry is not None and entry[0]() is w and entry[1] == key
+        bsize-64 quadrant gather) then runs in every fprop / bprop; the results are the same, only slower.
+        Under stream capture the entry is neither read nor replaced: a hit would leave the work out of the graph (a replay sees the
+        tensor's contents of that moment, not of the capture), a stored value would describe work that was recorded, not run -- ``make(True)``
+        answers what is right for any contents.  ``use=False`` never hits."""
+        if _capturing():
+            return make(True)
+        hit = store.get(name)
+        if not (use and hit is not None and hit[0]() is t and hit[1] == key):
+            hit = store[name] = (weakref.ref(t), key, make(False))
+        return hit[2]
 
     def invalidate_weights(self):
         """Forget everything derived from the CONTENTS of a tensor: the per-weights images (prepared pieces, quadrant views) and the
@@ -258,12 +264,8 @@ class BlocksparseMatMul(object):
         reference and compares identity) invalidates it.  Not used under autograd (the gather is part of the graph there)."""
         if w.requires_grad and torch.is_grad_enabled():
             return self._split64(w)
-        if _capturing():      # the gather becomes part of the graph (a replay sees the weights of that moment); the cache is neither read nor filled
-            return self._split64(w)
-        key = (w.data_ptr(), w._version, w.dtype, w.device)
-        if not self._same_weights(self._split64_hit, w, key):
-            self._split64_hit = (weakref.ref(w), key, self._split64(w))
-        return self._split64_hit[2]
+        # (under capture the gather becomes part of the graph: a replay sees the weights of that moment)
+        return self._per_tensor(vars(self), "_split64_hit", w, (w.data_ptr(), w._version, w.dtype, w.device), lambda capturing: self._split64(w))
 
     def _merge64(self, w32):
         _, inv = self._idx64(w32.device)
@@ -274,6 +276,22 @@ class BlocksparseMatMul(object):
             return None
         perm, _ = self._idx64(gate.device)
         return gate.index_select(0, perm // 4)
+
+    def _updat64(self, xs, dys, alpha, beta, dw, gate, sums_only, slot):
+        """``updat`` on the host-side quadrant view: the weight gradient of ``_inner`` over the same activations, put together as 64x64 blocks."""
+        if sums_only:                # the fp32 sums of the quadrants (a view of the inner call's workspace), put together as a copy
+            if gate is not None:
+                raise ValueError("updat(sums_only=True) returns the ungated sums: pass the gate to updat_finalize / DwReduce.start")
+            return self._merge64(self._inner.updat(xs, dys, sums_only=True, slot=slot))
+        if beta != 0.0 and dw is None:
+            raise ValueError("beta != 0 needs dw")
+        dw32 = self._inner.updat(xs, dys, alpha=alpha, beta=beta, dw=self._split64(dw) if (dw is not None and beta != 0.0) else None,
+                                 gate=self._gate64(self._check_gate(gate, xs[0].device)))
+        out = self._merge64(dw32)
+        if dw is not None:
+            dw.copy_(out)
+            return dw
+        return out
 
     # ---- shapes ----------------------------------------------------------------------------------
     def i_shape(self, N):
@@ -351,32 +369,31 @@ class BlocksparseMatMul(object):
         a = _lib.BsmmArgs.from_buffer_copy(cached)
         a.gate = None
         a.alpha, a.beta = 1.0, 0.0
-        ws = None
-        if need_ws:
-            # the scratch is shared by every call of this op on this stream (grown on demand): point the cached block at the current one
-            wkey = (lut_t.device.index, stream, op, slot)
-            ws = self._workspaces.get(wkey)
-            if ws is None or ws.numel() < need_ws:
-                ws = torch.empty(max(need_ws, 16), dtype=torch.uint8, device=lut_t.device)
-                self._workspaces[wkey] = ws
-            a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+        # the scratch is shared by every call of this op on this stream: point the copy at the current one
+        ws = self._scratch(lut_t.device, stream, op, slot, need_ws, a) if need_ws else None
         return a, ws, need_prep
 
-    def _workspace(self, a, op, device, slot=0):
-        """Device scratch for one call, kept per (device, stream, op) and grown on demand: the entry points never allocate, and
-        consecutive calls on a stream reuse the same bytes in stream order (nothing inside the timed region of a step)."""
-        need = _lib.load().bsmm_workspace_bytes(op, ctypes.byref(a))
-        if not need:
-            return None
-        key = (device.index, a.stream, op, slot)
+    def _scratch(self, device, stream, tag, slot, need, a=None):
+        """Device scratch of at least ``need`` bytes, kept per (device, stream, tag, slot) and grown on demand: the entry points never
+        allocate, and consecutive calls on a stream reuse the same bytes in stream order (nothing inside the timed region of a step).
+        ``a``: the argument block to point at it."""
+        key = (device.index, stream, tag, slot)
         ws = self._workspaces.get(key)
         if ws is None or ws.numel() < need:
-            ws = torch.empty(max(need, 16), dtype=torch.uint8, device=device)
-            self._workspaces[key] = ws
-        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+            ws = self._workspaces[key] = torch.empty(max(need, 16), dtype=torch.uint8, device=device)
+        if a is not None:
+            a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
         return ws
 
-    def _prepared(self, a, op, w):
+    def _prepared(self, a, op, w, need, capturing):
+        """bsmm_prepare_weights for this call, into ``need`` bytes: the stored entry's buffer where it is large enough, a fresh one
+        otherwise and always under capture."""
+        old = None if capturing else self._prepared_w.get(op)
+        buf = old[2] if (old is not None and old[2].numel() >= need) else torch.empty(need, dtype=torch.uint8, device=w.device)
+        _lib.check(_lib.load().bsmm_prepare_weights(op, w.data_ptr(), buf.data_ptr(), ctypes.byref(a)), "bsmm_prepare_weights")
+        return buf
+
+    def _prepared_cached(self, a, op, w):
         """The per-weights preparation of the library (bsmm_prepare_weights: fp32 / bsize 32 with a plan = the bf16 pieces of W), made
         once per (op, tensor OBJECT, version) and handed to the call in ``a.prepared_w`` -- W is constant across the calls of a
         pass; an in-place update (optimizer step: ``w._version`` changes) or any other tensor invalidates it.  The entry keeps a weak
@@ -385,26 +402,16 @@ class BlocksparseMatMul(object):
         A mutation the version counter cannot see (``w.data.add_()``) needs ``invalidate_weights()``; ``cache_prepared = False``
         prepares on every call.
 
-        Under stream capture the cache is neither read nor filled: a hit would leave the preparation out of the graph (a replay after an
-        optimizer step would multiply with the old pieces), a stored entry would describe work that was recorded, not run.  The pieces are
-        made inside the capture, into a buffer of the graph's own pool; the caller holds the returned buffer until its launch is recorded."""
-        lib = _lib.load()
-        need = lib.bsmm_prepared_bytes(op, ctypes.byref(a))
+        Under stream capture (``_per_tensor``: a hit would leave the preparation out of the graph, and a replay after an optimizer step
+        would multiply with the old pieces) the pieces are made inside the capture, into a buffer of the graph's own pool; the caller
+        holds the returned buffer until its launch is recorded."""
+        need = _lib.load().bsmm_prepared_bytes(op, ctypes.byref(a))
         if not need or w.data_ptr() % 16:      # (weights that are not 16-byte aligned: the library runs the V_FMA kernel, which takes no prepared pieces)
             return None
-        if _capturing():
-            buf = torch.empty(need, dtype=torch.uint8, device=w.device)
-            _lib.check(lib.bsmm_prepare_weights(op, w.data_ptr(), buf.data_ptr(), ctypes.byref(a)), "bsmm_prepare_weights")
-            a.prepared_w = buf.data_ptr()
-            return buf
-        key = (op, w.data_ptr(), w._version, a.stream)
-        hit = self._prepared_w.get(op)
-        if not (self.cache_prepared and self._same_weights(hit, w, key)):
-            buf = hit[2] if (hit is not None and hit[2].numel() >= need) else torch.empty(need, dtype=torch.uint8, device=w.device)
-            _lib.check(lib.bsmm_prepare_weights(op, w.data_ptr(), buf.data_ptr(), ctypes.byref(a)), "bsmm_prepare_weights")
-            hit = self._prepared_w[op] = (weakref.ref(w), key, buf)
-        a.prepared_w = hit[2].data_ptr()
-        return hit[2]
+        buf = self._per_tensor(self._prepared_w, op, w, (op, w.data_ptr(), w._version, a.stream),
+                               lambda capturing: self._prepared(a, op, w, need, capturing), use=self.cache_prepared)
+        a.prepared_w = buf.data_ptr()
+        return buf
 
     def _out_shape(self, x, feat_out):
         shp = list(x.shape)
@@ -436,31 +443,20 @@ class BlocksparseMatMul(object):
         the caller's promise instead, under capture too; a mutation the version counter cannot see needs ``invalidate_weights()``."""
         if self.gate_kind != "auto":
             return self.gate_kind
-        if _capturing():
-            return "general"
-        key = (gate.data_ptr(), gate._version)
-        hit = self._gate_kind_hit
-        if hit is not None and hit[0]() is gate and hit[1] == key:
-            return hit[2]
-        kind = "binary" if bool(((gate == 0) | (gate == 1)).all().item()) else "general"
-        self._gate_kind_hit = (weakref.ref(gate), key, kind)
-        return kind
+
+        def look(capturing):
+            return "binary" if not capturing and bool(((gate == 0) | (gate == 1)).all().item()) else "general"
+        return self._per_tensor(vars(self), "_gate_kind_hit", gate, (gate.data_ptr(), gate._version), look)
 
     def _doubled(self):
         """This operator over lut.double_tables(): 2 x blocks weight images [hi ; lo], fprop / bprop only, never gated itself."""
         d = self._dbl
         if d is None:
-            d = object.__new__(BlocksparseMatMul)
-            d.axis, d.bsize, d.z_order, d.segmented = self.axis, self.bsize, self.z_order, self.segmented
-            d.plan_options, d.updat_split, d.name = self.plan_options, self.updat_split, self.name + "/gated2"
-            d._dev_tables = d._ref_tables = _lut.double_tables(self._dev_tables)
-            d.blocks = 2 * self.blocks
-            d.w_shape, d.g_shape = (d.blocks, self.bsize, self.bsize), (d.blocks,)
-            d.CB, d.KB, d.C, d.K = self.CB, self.KB, self.C, self.K
-            d._device_cache, d._workspaces, d._args_cache, d._prepared_w = {}, {}, {}, {}
-            d.cache_prepared, d._inner, d._split64_hit, d.native64 = True, None, None, True
-            d.gate_images, d.gate_kind, d._gate_kind_hit, d._dbl, d._xprop_only = False, "general", None, None, True
-            self._dbl = d
+            d = self._dbl = type(self).__new__(type(self))      # (no layout of its own: the state of __init__ over the doubled tables)
+            tables = _lut.double_tables(self._dev_tables)
+            d._init_state(tables, tables, self.bsize, self.axis, self.z_order, self.name + "/gated2", self.segmented, self.plan_options,
+                          self.updat_split, xprop_only=True)
+            d.gate_images, d.gate_kind = False, "general"
         d.flow = self.flow
         return d
 
@@ -482,7 +478,7 @@ class BlocksparseMatMul(object):
         _lib.check(_lib.load().bsmm_gate_weights(w.data_ptr(), gate.data_ptr(), img.data_ptr(), self.blocks, self.bsize, _dtype_code(w.dtype), pieces, stream),
                    "bsmm_gate_weights")
         op = self if pieces == 1 else self._doubled()
-        return op.fprop(x, img) if which == "fprop" else op.bprop(x, img)
+        return op._xprop(which, x, img, None)
 
     # ---- the three passes ------------------------------------------------------------------------
     def _xprop_plan(self, tabs, which, N, n_out_features, dtype, gate):
@@ -500,57 +496,46 @@ class BlocksparseMatMul(object):
     def fprop(self, x, w, gate=None):
         """Y = fprop(X, W): axis 0 Y(K,N) = Wd^T X, axis 1 Y(N,K) = X Wd (op BlocksparseMatmul).
         ``gate`` (float32 [blocks]): block w contributes gate[w] times its product, gate 0 = skipped."""
-        self._check_tensor(x, "x"); self._check_tensor(w, "w")
-        gate = self._check_gate(gate, x.device)
-        if x.dtype != w.dtype:
-            raise TypeError("x and w must have the same dtype")
-        if self._inner is not None and not self.native64:
-            return self._inner.fprop(x, self._split64_cached(w), gate=self._gate64(gate))
-        x = x.contiguous(); w = w.contiguous()
-        N = self._n_of(x, self.C)
-        if gate is not None:
-            y = self._gated_xprop("fprop", x, w, gate, N)
-            if y is not None:
-                return y
-        lib = _lib.load()
-        tabs = self._tables_on(x.device)
-        y = torch.empty(self._out_shape(x, self.K), dtype=x.dtype, device=x.device)
-        plan = self._xprop_plan(tabs, "fprop", N, self.K, x.dtype, gate)
-        a, _, need_prep = self._call_args(_lib.OP_FPROP, tabs, tabs.fprop, self._dev_tables["fprop"], N, self.C, self.K, x.dtype, plan, gated=gate is not None)
-        a.gate = gate.data_ptr() if gate is not None else None
-        if need_prep:
-            a.prepared_w = None
-            held = self._prepared(a, _lib.OP_FPROP, w)      # (held until the launch below is on the stream)
-            self._workspace(a, _lib.OP_FPROP, x.device)
-        _lib.check(lib.bsmm_fprop(x.data_ptr(), w.data_ptr(), y.data_ptr(), ctypes.byref(a)), "bsmm_fprop")
-        return y
+        return self._xprop("fprop", x, w, gate)
 
     def bprop(self, dy, w, gate=None):
         """DX = bprop(DY, W) (op BlocksparseMatmulDX; C and K swapped as in matmul.py:506-510); ``gate`` as in fprop."""
-        self._check_tensor(dy, "dy"); self._check_tensor(w, "w")
-        gate = self._check_gate(gate, dy.device)
-        if dy.dtype != w.dtype:
-            raise TypeError("dy and w must have the same dtype")
+        return self._xprop("bprop", dy, w, gate)
+
+    # what tells the two passes apart; the lookup table, its side table and the plans are found under the pass' name
+    # pass -> (op code, the input's name in messages, attributes with the input / output feature counts, entry point of the library)
+    _XPROP = {"fprop": (_lib.OP_FPROP, "x", "C", "K", "bsmm_fprop"), "bprop": (_lib.OP_BPROP, "dy", "K", "C", "bsmm_bprop")}
+
+    def _xprop(self, which, inp, w, gate):
+        """fprop / bprop: one call of the library over this operator's ``which`` tables."""
+        op, what, feat_in, feat_out, entry = self._XPROP[which]
+        feat_in, feat_out = getattr(self, feat_in), getattr(self, feat_out)
+        self._check_tensor(inp, what); self._check_tensor(w, "w")
+        gate = self._check_gate(gate, inp.device)
+        if inp.dtype != w.dtype:
+            raise TypeError("%s and w must have the same dtype" % what)
         if self._inner is not None and not self.native64:
-            return self._inner.bprop(dy, self._split64_cached(w), gate=self._gate64(gate))
-        dy = dy.contiguous(); w = w.contiguous()
-        N = self._n_of(dy, self.K)
+            return self._inner._xprop(which, inp, self._split64_cached(w), self._gate64(gate))
+        inp = inp.contiguous(); w = w.contiguous()
+        N = self._n_of(inp, feat_in)
         if gate is not None:
-            dx = self._gated_xprop("bprop", dy, w, gate, N)
-            if dx is not None:
-                return dx
+            out = self._gated_xprop(which, inp, w, gate, N)
+            if out is not None:
+                return out
         lib = _lib.load()
-        tabs = self._tables_on(dy.device)
-        dx = torch.empty(self._out_shape(dy, self.C), dtype=dy.dtype, device=dy.device)
-        plan = self._xprop_plan(tabs, "bprop", N, self.C, dy.dtype, gate)
-        a, _, need_prep = self._call_args(_lib.OP_BPROP, tabs, tabs.bprop, self._dev_tables["bprop"], N, self.K, self.C, dy.dtype, plan, gated=gate is not None)
+        tabs = self._tables_on(inp.device)
+        out = torch.empty(self._out_shape(inp, feat_out), dtype=inp.dtype, device=inp.device)
+        plan = self._xprop_plan(tabs, which, N, feat_out, inp.dtype, gate)
+        a, _, need_prep = self._call_args(op, tabs, getattr(tabs, which), self._dev_tables[which], N, feat_in, feat_out, inp.dtype, plan, gated=gate is not None)
         a.gate = gate.data_ptr() if gate is not None else None
         if need_prep:
             a.prepared_w = None
-            held = self._prepared(a, _lib.OP_BPROP, w)      # (held until the launch below is on the stream)
-            self._workspace(a, _lib.OP_BPROP, dy.device)
-        _lib.check(lib.bsmm_bprop(dy.data_ptr(), w.data_ptr(), dx.data_ptr(), ctypes.byref(a)), "bsmm_bprop")
-        return dx
+            held = self._prepared_cached(a, op, w)      # (held until the launch below is on the stream)
+            need_ws = lib.bsmm_workspace_bytes(op, ctypes.byref(a))      # (sized now that prepared_w is set)
+            if need_ws:
+                self._scratch(inp.device, a.stream, op, 0, need_ws, a)
+        _lib.check(getattr(lib, entry)(inp.data_ptr(), w.data_ptr(), out.data_ptr(), ctypes.byref(a)), entry)
+        return out
 
     def updat(self, xs, dys, alpha=1.0, beta=0.0, dw=None, gate=None, sums_only=False, slot=0):
         """DW = alpha * sum_p updat(X_p, DY_p) + beta * DW  (ops BlocksparseMatmulDW / ...DWA).
@@ -588,19 +573,7 @@ class BlocksparseMatMul(object):
                         and not (_lib.call_flags() & (_lib.FLAG_NO_PLAN | _lib.FLAG_FORCE_VALU))
                         and (self.plan_options & 0xf0) in (0, _lib.PLAN_STREAM_16, _lib.PLAN_STREAM_8, _lib.PLAN_STREAM_32))
         if self._inner is not None and not native64:
-            if sums_only:                # the fp32 sums of the quadrants (a view of the inner call's workspace), put together as a copy
-                if gate is not None:
-                    raise ValueError("updat(sums_only=True) returns the ungated sums: pass the gate to updat_finalize / DwReduce.start")
-                return self._merge64(self._inner.updat(xs, dys, sums_only=True, slot=slot))
-            if beta != 0.0 and dw is None:
-                raise ValueError("beta != 0 needs dw")
-            dw32 = self._inner.updat(xs, dys, alpha=alpha, beta=beta, dw=self._split64(dw) if (dw is not None and beta != 0.0) else None,
-                                     gate=self._gate64(self._check_gate(gate, xs[0].device)))
-            out = self._merge64(dw32)
-            if dw is not None:
-                dw.copy_(out)
-                return dw
-            return out
+            return self._updat64(xs, dys, alpha, beta, dw, gate, sums_only, slot)
         lib = _lib.load()
         dev = xs[0].device
         tabs = self._tables_on(dev)
@@ -635,10 +608,8 @@ class BlocksparseMatMul(object):
         xp = arr(*[t.data_ptr() for t in xs])
         ep = arr(*[t.data_ptr() for t in dys])
         rc = lib.bsmm_updat(xp, ep, dw.data_ptr() if dw is not None else None, ctypes.byref(a))
-        if rc == -2 and self._inner is not None and not sums_only:      # BSMM_ERR_UNSUPPORTED from the composite path: quadrant view
-            dw32 = self._inner.updat(xs, dys, alpha=alpha, beta=beta, dw=self._split64(dw) if beta != 0.0 else None, gate=self._gate64(gate))
-            dw.copy_(self._merge64(dw32))
-            return dw
+        if rc == _lib.ERR_UNSUPPORTED and self._inner is not None and not sums_only:      # refused by the composite path: quadrant view, into this dw
+            return self._updat64(xs, dys, alpha, beta, dw, gate, False, slot)
         _lib.check(rc, "bsmm_updat")
         if sums_only:
             n = self.blocks * self.bsize * self.bsize
@@ -717,12 +688,9 @@ class BlocksparseMatMul(object):
 
     def _l2_tables(self, device):
         key = ("l2", str(device))
-        t = self._l2_dev.get(key) if hasattr(self, "_l2_dev") else None
+        t = self._l2_dev.get(key)
         if t is None:
-            if not hasattr(self, "_l2_dev"):
-                self._l2_dev = {}
-            t = torch.from_numpy(np.ascontiguousarray(self.l2_lut)).to(device)
-            self._l2_dev[key] = t
+            t = self._l2_dev[key] = torch.from_numpy(np.ascontiguousarray(self.l2_lut)).to(device)
         return t
 
     def _l2_fwd(self, W, gain, epsilon, y_dtype):

@@ -37,11 +37,7 @@ except Exception:  # pragma: no cover
     torch = None
 
 _BSIZES = (8, 16, 32, 64)
-
-
-def _dtype_code(dt):
-    from .matmul import _dtype_code as code
-    return code(dt)
+_dtype_code = _lib.require_dtype_code
 
 
 def _on_device(t, what):

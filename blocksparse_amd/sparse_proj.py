@@ -15,7 +15,7 @@ OP_GAT, OP_SCT, OP_ADD, OP_MUL = 0, 1, 2, 3
 
 
 def _code(dt):
-    return {torch.float32: _lib.F32, torch.float16: _lib.F16, torch.bfloat16: _lib.BF16}[dt]
+    return _lib.require_dtype_code(dt, KeyError)
 
 
 class SparseProj(object):

@@ -27,11 +27,7 @@ except Exception:  # pragma: no cover
     torch = None
 
 _BSIZES = (8, 16, 32, 64)
-
-
-def _dtype_code(dt):
-    from .matmul import _dtype_code as code
-    return code(dt)
+_dtype_code = _lib.require_dtype_code
 
 
 def _norm_code(norm):
@@ -127,22 +123,14 @@ def feature_reduce(ts, bsize, axis, norm="max"):
     return out
 
 
-def _rdw_workspace(bsmm, device, need):
-    key = (device.index, _lib.raw_stream(device), "reduced_dw")
-    ws = bsmm._workspaces.get(key)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=device)
-        bsmm._workspaces[key] = ws
-    return ws
-
-
 def reduced_dw(bsmm, x_red, y_red, dw, scale, accumulate):
     """Stage 2 (bsmm_reduced_dw) into ``dw`` (fp32 [CB, KB])."""
     lib = _lib.load()
     CB, KB, Kc = x_red.shape[0], y_red.shape[0], x_red.shape[1] * x_red.shape[2]
-    ws = _rdw_workspace(bsmm, dw.device, int(lib.bsmm_reduced_dw_workspace_bytes(CB, KB, Kc)))
+    stream = _lib.raw_stream(dw.device)
+    ws = bsmm._scratch(dw.device, stream, "reduced_dw", 0, int(lib.bsmm_reduced_dw_workspace_bytes(CB, KB, Kc)))
     _lib.check(lib.bsmm_reduced_dw(x_red.data_ptr(), y_red.data_ptr(), dw.data_ptr(), CB, KB, Kc, float(scale), 1 if accumulate else 0,
-                                   _dtype_code(x_red.dtype), ws.data_ptr(), ws.numel(), _lib.raw_stream(dw.device)), "bsmm_reduced_dw")
+                                   _dtype_code(x_red.dtype), ws.data_ptr(), ws.numel(), stream), "bsmm_reduced_dw")
     return dw
 
 
@@ -183,7 +171,7 @@ def _exact_norms(bsmm, xs, dys, norm):
             sums = twin.updat(xs[i:i + 8], dys[i:i + 8], sums_only=True)
             total = sums.clone() if total is None else total.add_(sums)
     except _lib.BsmmError as e:          # ... else (BSMM_ERR_UNSUPPORTED, refused before any launch) the fp32 weight gradient of fp32 copies of the
-        if e.code != -2:                 # activations: the norm of a gradient rounded to bf16 would be off by up to 2^-9 per block
+        if e.code != _lib.ERR_UNSUPPORTED:   # activations: the norm of a gradient rounded to bf16 would be off by up to 2^-9 per block
             raise
         total = twin.updat_grouped([t.float() for t in xs], [t.float() for t in dys], group_size=8)
     norms = blocksparse_norm(total, norm=norm)

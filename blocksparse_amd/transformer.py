@@ -21,13 +21,7 @@ _MASK_TORCH = {64: "int64", 32: "int32", 16: "int16", 8: "uint8"}
 
 
 def _code(dt):
-    if dt == torch.float32:
-        return _lib.F32
-    if dt == torch.float16:
-        return _lib.F16
-    if dt == torch.bfloat16:
-        return _lib.BF16
-    raise TypeError("blocksparse_amd: unsupported dtype %s" % dt)
+    return _lib.require_dtype_code(dt, lambda d: TypeError("blocksparse_amd: unsupported dtype %s" % d))
 
 
 def build_bst_tables(layout):
@@ -218,7 +212,7 @@ class BlocksparseTransformer(object):
         mp = mask_t.data_ptr() if mask_t is not None else None
         mh = mask_t.shape[0] if mask_t is not None else 1
         rc = _lib.load().bst_nt_softmax(q.data_ptr(), k.data_ptr(), y.data_ptr(), mp, mh, float(scale), int(self.nn_max), ctypes.byref(args))
-        if rc == -2:                                                           # BSMM_ERR_UNSUPPORTED
+        if rc == _lib.ERR_UNSUPPORTED:
             return None
         _lib.check(rc, "bst_nt_softmax")
         return y
@@ -235,7 +229,7 @@ class BlocksparseTransformer(object):
         dx = torch.empty_like(y)
         args = self._args(lut, e.shape[0], hs, _code(e.dtype), _code(y.dtype))
         rc = _lib.load().bst_nt_softmax_grad(e.data_ptr(), v.data_ptr(), y.data_ptr(), dx.data_ptr(), float(scale), int(self.nn_max), ctypes.byref(args))
-        if rc == -2:
+        if rc == _lib.ERR_UNSUPPORTED:
             return None
         _lib.check(rc, "bst_nt_softmax_grad")
         return dx
