@@ -287,4 +287,85 @@ __device__ __forceinline__ uint32_t lds_addr_of(const void* p) {
     return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const void*)p;
 }
 
+// a wave-uniform pointer, provably so for the compiler (an "s" asm operand fed from a value it regards as divergent is
+// emitted as a VGPR and does not assemble)
+__device__ __forceinline__ const void* uniform_ptr(const void* p) {
+    const uint64_t v = reinterpret_cast<uint64_t>(p);
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+    return reinterpret_cast<const void*>(((uint64_t)hi << 32) | lo);
+}
+
+// LDS-DMA with a scalar base and a 32-bit per-lane byte offset (saddr form): no 64-bit address VGPRs in the loop.
+__device__ __forceinline__ void glds16_saddr(const void* sbase, uint32_t voff, uint32_t lds_byte_addr) {
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(voff), "s"(sbase), "s"(lds_byte_addr)
+                 : "memory");
+}
+// NI consecutive 1 KiB pieces (LDS dst, dst + 1 KiB) from one scalar base: M0 is saved / restored once and stepped with a
+// scalar add; 5 scalar instructions for two DMAs.  (The CU has ONE scalar unit for its 16 waves: the ~40 scalar instructions
+// per wave and interval of the first streaming weight-gradient kernel cost ~600 cycles per interval, more than the matrix work.)
+__device__ __forceinline__ void glds16_saddr_x2(const void* sbase, uint32_t voff0, uint32_t voff1, uint32_t lds_byte_addr) {
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\t"
+                 "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(voff0), "v"(voff1), "s"(sbase), "s"(lds_byte_addr)
+                 : "memory", "scc");      // (s_add_u32 writes SCC: without the clobber a compare hoisted above the block loses its result)
+}
+
+__device__ __forceinline__ void glds16_saddr_x4(const void* sbase, uint32_t v0, uint32_t v1, uint32_t v2, uint32_t v3, uint32_t lds_byte_addr) {
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %6\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %5\n\t"
+                 "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %5\n\t"
+                 "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, %5\n\t"
+                 "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %4, %5\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(v0), "v"(v1), "v"(v2), "v"(v3), "s"(sbase), "s"(lds_byte_addr)
+                 : "memory", "scc");
+}
+
+// entry `idx` (wave-uniform, runtime) of a pointer list that lives in kernel-argument SGPRs: a chain of scalar selects
+// (a dynamic index would make the compiler copy the list to scratch memory and read it back with vector loads)
+__device__ __forceinline__ const unsigned char* pick_ptr(const PtrList8& l, int idx) {
+    const void* p = l.p[0];
+#pragma unroll
+    for (int k = 1; k < 8; ++k) p = (idx == k) ? l.p[k] : p;
+    return static_cast<const unsigned char*>(p);
+}
+
+// The gfx950 transposing LDS read ds_read_b64_tr_b16: within a 16-lane group, lane t receives column t of the 4 x 16 (b16) matrix
+// the group's lanes point at -- four consecutive K for one feature (probed on hardware: profiles/r01_tr_probe.log; the access
+// patterns are explained in bsmm_updat_tr.h).
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ uint2 ds_tr16(const unsigned char* p) {
+    s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p);
+    return __builtin_bit_cast(uint2, v);
+}
+// the 16-byte fragment of a K = 32 MFMA operand (8 consecutive K of this lane's feature): two transposing reads four slab rows apart,
+// `row_bytes` = the slab's row stride
+__device__ __forceinline__ uint4 ds_tr16_frag(const unsigned char* p, int row_bytes) {
+    const uint2 lo = ds_tr16(p), hi = ds_tr16(p + 4 * row_bytes);
+    return make_uint4(lo.x, lo.y, hi.x, hi.y);
+}
+
+// two floats rounded to the 16-bit type of DT in one dword, `a` in bits 0..15
+template <class DT>
+__device__ __forceinline__ uint32_t pack_pair(float a, float b) {
+    return (uint32_t)DT::from_f32(a) | ((uint32_t)DT::from_f32(b) << 16);
+}
+
+__device__ __forceinline__ void zero_tile(f32x16& acc) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+}
+__device__ __forceinline__ void zero_tile(f32x4& acc) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) acc[i] = 0.f;
+}
+
+// this wave's index in its workgroup, in a scalar register
+__device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); }
+
 }  // namespace bsmm

@@ -81,8 +81,8 @@ gather8_kernel(const float* __restrict__ S32, const int32_t* __restrict__ plan, 
         o[3] += beta * DT::to_f32((typename DT::T)(old.y >> 16));
     }
     uint2 r;
-    r.x = (uint32_t)DT::from_f32(o[0]) | ((uint32_t)DT::from_f32(o[1]) << 16);
-    r.y = (uint32_t)DT::from_f32(o[2]) | ((uint32_t)DT::from_f32(o[3]) << 16);
+    r.x = pack_pair<DT>(o[0], o[1]);
+    r.y = pack_pair<DT>(o[2], o[3]);
     *reinterpret_cast<uint2*>(dst) = r;
 }
 

@@ -40,8 +40,7 @@ updat32_kernel(PtrList8 Xs, PtrList8 Es, typename DT::T* __restrict__ DW, const 
     if (gate) alpha *= gate[w];                       // gated dw (updat_test(dw_gated=True), blocksparse/matmul.py:412-418)
 
     f32x16 acc;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+    zero_tile(acc);
 
     for (int p = 0; p < pcount; ++p) {
         const T* X = static_cast<const T*>(Xs.p[p]);
@@ -349,7 +348,7 @@ updat_a0_wave_kernel(PtrList8 Xs, PtrList8 Es, typename DT::T* __restrict__ DW, 
         const int r = lane & 31, h = lane >> 5;                  // A[m = ci][k = n]: lane (ci = r, K half h) holds columns 16 s + 8 h ..
         f32x16 acc;
 #pragma unroll
-        for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+        for (int i = 0; i < 16; ++i) acc[i] = 0.f;   // (spelled out: zero_tile() changes this kernel's instruction order, profiles/device_prims_isa.md)
         for (int p = 0; p < pcount; ++p) {
             const T* X = static_cast<const T*>(Xs.p[p]) + (size_t)(c * 32 + r) * N;
             const T* E = static_cast<const T*>(Es.p[p]) + (size_t)(k * 32 + r) * N;

@@ -95,7 +95,7 @@ updat16_rows_kernel(PtrList8 Xs, PtrList8 Es, typename DT::T* __restrict__ DW, f
     if (it >= sec[4]) return;
     const int32_t* item = sec + U6_HDR + (size_t)it * U6_ITEM;
     const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wave = wave_id();
     const int c0 = item[0], k0 = item[1];
     const int32_t* wv = item + 4 + wave * U6_WAVE;
     const uint32_t rowsw = (uint32_t)wv[0];

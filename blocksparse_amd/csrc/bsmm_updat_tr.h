@@ -18,16 +18,9 @@
 
 namespace bsmm {
 
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-
 constexpr int UT_D = 4;              // ring depth (chunks)
 constexpr int UT_SLOT = 2 * 2048;    // bytes per ring slot: X slab (32 rows x 64 B) + DY slab
 constexpr int UT_LDS = 4 * UT_D * UT_SLOT;
-
-__device__ __forceinline__ uint2 ds_tr16(const unsigned char* p) {
-    s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p);
-    return __builtin_bit_cast(uint2, v);
-}
 
 template <class DT>
 __global__ void __launch_bounds__(256, 2)
@@ -39,7 +32,7 @@ updat32_a1_tr_kernel(PtrList8 Xs, PtrList8 Es, typename DT::T* __restrict__ DW, 
     const int w = updat_block(blockIdx.x, blocks);
     if (w < 0) return;
     const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wave = wave_id();
     const int c = lut[2 * w], k = lut[2 * w + 1];
 
     unsigned char* ring = smem + wave * (UT_D * UT_SLOT);
@@ -54,7 +47,7 @@ updat32_a1_tr_kernel(PtrList8 Xs, PtrList8 Es, typename DT::T* __restrict__ DW, 
 
     f32x16 acc;
 #pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+    for (int i = 0; i < 16; ++i) acc[i] = 0.f;   // (spelled out: zero_tile() changes this kernel's instruction order, profiles/device_prims_isa.md)
 
     const int nchunks = (N + 31) >> 5;
     for (int p = 0; p < pcount; ++p) {
@@ -85,10 +78,8 @@ updat32_a1_tr_kernel(PtrList8 Xs, PtrList8 Es, typename DT::T* __restrict__ DW, 
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk) {     // K sub-block kk: rows 16kk + 8h + {0..3 | 4..7}
                 const unsigned char* sp = slot + (16 * kk + 8 * h) * 64 + rd_base;
-                const uint2 a0 = ds_tr16(sp), a1 = ds_tr16(sp + 4 * 64);
-                const uint2 b0 = ds_tr16(sp + 2048), b1 = ds_tr16(sp + 2048 + 4 * 64);
-                a[kk] = make_uint4(a0.x, a0.y, a1.x, a1.y);
-                b[kk] = make_uint4(b0.x, b0.y, b1.x, b1.y);
+                a[kk] = ds_tr16_frag(sp, 64);
+                b[kk] = ds_tr16_frag(sp + 2048, 64);
             }
             if (n0 + 32 > N) {   // ragged tail: rows >= N were clamped re-reads -> zero their contribution (A side suffices)
 #pragma unroll
@@ -146,7 +137,7 @@ updat32_a1_small_kernel(PtrList8 Xs, PtrList8 Es, typename DT::T* __restrict__ D
     static_assert(DT::is16, "transposing-read kernel: 16-bit storage types");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (spelled out: wave_id() changes this kernel's instruction order, profiles/device_prims_isa.md)
     const int groups = (blocks + 3) >> 2;                                  // workgroups with work; XCD x walks a contiguous range of them
     const int g = updat_block(blockIdx.x, groups);
     if (g < 0) return;
@@ -162,7 +153,7 @@ updat32_a1_small_kernel(PtrList8 Xs, PtrList8 Es, typename DT::T* __restrict__ D
 
     f32x16 acc;
 #pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+    for (int i = 0; i < 16; ++i) acc[i] = 0.f;   // (spelled out, as the wave id above: profiles/device_prims_isa.md)
     const int nchunks = (N + 31) >> 5;
     for (int p = 0; p < pcount; ++p) {
         const T* X = static_cast<const T*>(Xs.p[p]) + c * 32 + dpiece * 8;
@@ -190,10 +181,8 @@ updat32_a1_small_kernel(PtrList8 Xs, PtrList8 Es, typename DT::T* __restrict__ D
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk) {
                 const unsigned char* sp = slot + (16 * kk + 8 * h) * 64 + rd_base;
-                const uint2 a0 = ds_tr16(sp), a1 = ds_tr16(sp + 4 * 64);
-                const uint2 b0 = ds_tr16(sp + 2048), b1 = ds_tr16(sp + 2048 + 4 * 64);
-                a[kk] = make_uint4(a0.x, a0.y, a1.x, a1.y);
-                b[kk] = make_uint4(b0.x, b0.y, b1.x, b1.y);
+                a[kk] = ds_tr16_frag(sp, 64);
+                b[kk] = ds_tr16_frag(sp + 2048, 64);
             }
             if (n0 + 32 > N) {   // ragged tail: rows >= N were clamped re-reads -> zero their contribution (A side suffices)
 #pragma unroll
@@ -242,7 +231,7 @@ updat16_a1_tr_kernel(PtrList8 Xs, PtrList8 Es, typename DT::T* __restrict__ DW, 
     const int w = updat_block(blockIdx.x, blocks);
     if (w < 0) return;
     const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wave = wave_id();
     const int c = lut[2 * w], k = lut[2 * w + 1];
     unsigned char* ring = smem + wave * (UT16_D * UT16_SLOT);
     const uint32_t ring_addr = lds_addr_of(ring);
@@ -272,10 +261,8 @@ updat16_a1_tr_kernel(PtrList8 Xs, PtrList8 Es, typename DT::T* __restrict__ DW, 
             rd_pos = (rd_pos + 1) & (UT16_D - 1);
             wr_pos = (wr_pos + 1) & (UT16_D - 1);
             const int n0 = (wave + 4 * qq) * 32;
-            const uint2 a0 = ds_tr16(slot + rd_base), a1 = ds_tr16(slot + rd_base + 4 * 32);
-            const uint2 b0 = ds_tr16(slot + 1024 + rd_base), b1 = ds_tr16(slot + 1024 + rd_base + 4 * 32);
-            uint4 a = make_uint4(a0.x, a0.y, a1.x, a1.y);
-            const uint4 b = make_uint4(b0.x, b0.y, b1.x, b1.y);
+            uint4 a = ds_tr16_frag(slot + rd_base, 32);
+            const uint4 b = ds_tr16_frag(slot + 1024 + rd_base, 32);
             if (n0 + 32 > N) {
                 const int nb = n0 + 8 * q;
                 uint32_t* u = reinterpret_cast<uint32_t*>(&a);

@@ -32,7 +32,6 @@
 
 #include "bsmm_common.h"
 #include "bsmm_plan.h"
-#include "bsmm_updat_tr.h"
 
 namespace bsmm {
 
@@ -64,12 +63,9 @@ constexpr int U2_CH0 = 32;                 // minibatch columns per chunk
 // at 10 / 20 / 50 % against 120 / 129 / 270 for the windowed kernel of round 1 -- and 71 / 95 / 174 on feature axis 1 for the same bytes.  The
 // counters say why (profiles/r03_pmc_updat_a0_a1.txt): the L1 sends one L2 request per 64 contiguous bytes, 17.7 M requests against 8.7 M, and
 // the per-CU request rate is what bounds these kernels; 128-byte row pieces (64 columns) would need 128 KiB per chunk of a 512 x 512 window.
-// -DU2_RING5=1: FIVE half slots (X of chunk k in half slot 2k mod 5, DY in 2k + 1 mod 5; X requested two chunks ahead, DY one: 1.5 chunks
-// always in flight) -- measured 109 / 129 / 192: more data in flight does not help a request-rate bound.
-#ifndef U2_RING5
-#define U2_RING5 0
-#endif
-constexpr int u2_lds_bytes0(int ws) { return U2_RING5 ? 5 * ws * 32 * (U2_CH0 * 2) : 131072; }
+// (A ring of FIVE half slots -- X of chunk k in half slot 2k mod 5, DY in 2k + 1 mod 5; X requested two chunks ahead, DY one: 1.5 chunks
+// always in flight -- measured 109 / 129 / 192, profiles/r03_updat_a0_stream_ring5.txt: more data in flight does not help a request-rate bound.)
+constexpr int u2_lds_bytes0(int /*ws*/) { return 131072; }
 
 #ifdef U2_STAMPS
 // wall-clock stamps (s_memrealtime, 100 MHz, one clock for the chip) of wave 0 of every workgroup: [0] start, [1] chunk loop of its first range
@@ -80,54 +76,6 @@ __device__ unsigned long long g_u2_trace[1024 * 8];
 #else
 #define U2_STAMP(k, v) do { } while (0)
 #endif
-
-// a wave-uniform pointer, provably so for the compiler (an "s" asm operand fed from a value it regards as divergent is
-// emitted as a VGPR and does not assemble)
-__device__ __forceinline__ const void* uniform_ptr(const void* p) {
-    const uint64_t v = reinterpret_cast<uint64_t>(p);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    return reinterpret_cast<const void*>(((uint64_t)hi << 32) | lo);
-}
-
-// LDS-DMA with a scalar base and a 32-bit per-lane byte offset (saddr form): no 64-bit address VGPRs in the loop.
-__device__ __forceinline__ void glds16_saddr(const void* sbase, uint32_t voff, uint32_t lds_byte_addr) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(voff), "s"(sbase), "s"(lds_byte_addr)
-                 : "memory");
-}
-// NI consecutive 1 KiB pieces (LDS dst, dst + 1 KiB) from one scalar base: M0 is saved / restored once and stepped with a
-// scalar add; 5 scalar instructions for two DMAs.  (The CU has ONE scalar unit for its 16 waves: the ~40 scalar instructions
-// per wave and interval of the first version cost ~600 cycles per interval, more than the matrix work.)
-__device__ __forceinline__ void glds16_saddr_x2(const void* sbase, uint32_t voff0, uint32_t voff1, uint32_t lds_byte_addr) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\t"
-                 "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(voff0), "v"(voff1), "s"(sbase), "s"(lds_byte_addr)
-                 : "memory", "scc");      // (s_add_u32 writes SCC: without the clobber a compare hoisted above the block loses its result)
-}
-
-__device__ __forceinline__ void glds16_saddr_x4(const void* sbase, uint32_t v0, uint32_t v1, uint32_t v2, uint32_t v3, uint32_t lds_byte_addr) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %6\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %5\n\t"
-                 "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %5\n\t"
-                 "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, %5\n\t"
-                 "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %4, %5\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(v0), "v"(v1), "v"(v2), "v"(v3), "s"(sbase), "s"(lds_byte_addr)
-                 : "memory", "scc");
-}
-
-// entry `idx` (wave-uniform, runtime) of a pointer list that lives in kernel-argument SGPRs: a chain of scalar selects
-// (a dynamic index would make the compiler copy the list to scratch memory and read it back with vector loads)
-__device__ __forceinline__ const unsigned char* pick_ptr(const PtrList8& l, int idx) {
-    const void* p = l.p[0];
-#pragma unroll
-    for (int k = 1; k < 8; ++k) p = (idx == k) ? l.p[k] : p;
-    return static_cast<const unsigned char*>(p);
-}
 
 // DIRECT blocks (bsmm_plan.h, 'BSU2' version 3; feature axis 1): workgroup `e` behind the schedule's multiplies quarter e % U2_DIRECT_PARTS of the
 // minibatch for direct block e / U2_DIRECT_PARTS -- the block's own 64-byte row pieces only (the per-block scheme of bsmm_updat_tr.h): wave v takes
@@ -141,7 +89,7 @@ __device__ __forceinline__ void u2_direct_block(const PtrList8& Xs, const PtrLis
     constexpr int SLOT = 2048, D = LDSB / U2_WAVES / SLOT;       // ring slots per wave: 4 (128 KiB) or 2 (64 KiB)
     static_assert(D >= 2 && LDSB >= U2_WAVES * 4096, "direct blocks: a ring of two chunks per wave and 64 KiB for the reduction");
     const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wave = wave_id();
     const int DP = plan[30];
     const int d = e / DP, q = e - d * DP;
     const int32_t* de = plan + plan[29] + 4 * d;
@@ -152,8 +100,7 @@ __device__ __forceinline__ void u2_direct_block(const PtrList8& Xs, const PtrLis
     const int g16 = lane >> 4, t16 = lane & 15, h = g16 >> 1;     // fragments: as updat32_a1_tr_kernel
     const int rd_base = (8 * h + (t16 >> 2)) * 64 + (16 * (g16 & 1) + 4 * (t16 & 3)) * 2;
     f32x16 acc;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+    zero_tile(acc);
     const int nch = (N + 15) >> 4;
     const int lo = (int)((long)nch * q / DP), hi = (int)((long)nch * (q + 1) / DP);
     const int first = lo + wave;
@@ -176,9 +123,8 @@ __device__ __forceinline__ void u2_direct_block(const PtrList8& Xs, const PtrLis
             const unsigned char* sp = ring + rd_pos * SLOT + rd_base;
             rd_pos = (rd_pos + 1 == D) ? 0 : rd_pos + 1;
             wr_pos = (wr_pos + 1 == D) ? 0 : wr_pos + 1;
-            const uint2 a0 = ds_tr16(sp), a1 = ds_tr16(sp + 4 * 64), b0 = ds_tr16(sp + 1024), b1 = ds_tr16(sp + 1024 + 4 * 64);
-            uint4 a = make_uint4(a0.x, a0.y, a1.x, a1.y);
-            const uint4 b = make_uint4(b0.x, b0.y, b1.x, b1.y);
+            uint4 a = ds_tr16_frag(sp, 64);
+            const uint4 b = ds_tr16_frag(sp + 1024, 64);
             const int nb = (first + U2_WAVES * j) * 16 + 8 * h;      // K index i of this lane's fragment is row nb + i
             if (nb + 8 > N) {                                        // ragged tail: rows >= N were clamped re-reads
                 uint32_t* u = reinterpret_cast<uint32_t*>(&a);
@@ -216,7 +162,6 @@ updat32_a1_v2_kernel(PtrList8 Xs, PtrList8 Es, typename DT::T* __restrict__ DW, 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int CH = AXIS == 1 ? U2_CH : U2_CH0;                // minibatch entries per chunk
     constexpr int KS = CH / 16;                                   // MFMA K-steps per chunk
-    constexpr bool FIVE = AXIS == 0 && U2_RING5;                  // axis 0, experiment: five HALF slots instead (see u2_lds_bytes0)
     constexpr int D = AXIS == 1 ? u2_ring(WS) : (WS == 16 ? 2 : 4);   // ring slots (axis 0: 64 / 32 KiB each)
     constexpr int AHEAD = D / 2;                                  // prefetch distance in chunks
     constexpr int ROWB = AXIS == 1 ? WS * 64 : CH * 2;            // bytes per slab row
@@ -236,7 +181,7 @@ updat32_a1_v2_kernel(PtrList8 Xs, PtrList8 Es, typename DT::T* __restrict__ DW, 
         return;
     }
     const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wave = wave_id();
     const int32_t* items = plan + plan[6];
     const int nchunks = (N + CH - 1) / CH;
     const int nfull = N / CH;                                                 // chunks of a pair with all CH rows / columns
@@ -266,8 +211,7 @@ updat32_a1_v2_kernel(PtrList8 Xs, PtrList8 Es, typename DT::T* __restrict__ DW, 
     auto row_of = [&](int q) -> int { return ROWB <= 1024 ? d_row0 + q * RPI : (ii0 + q) / IPR; };          // slab row of my instruction q
     auto pos_of = [&](int q) -> int { return ROWB <= 1024 ? lane % PPR : ((ii0 + q) % IPR) * 64 + lane; };  // LDS piece of the row this lane fills
     const uint32_t sub_off = ii0 * 1024;                                      // my first piece inside my operand's slab
-    const uint32_t wave_off = (!FIVE ? opE * SLAB : 0) + sub_off;         // ... inside a ring slot (five half slots: the half slot carries the operand)
-    constexpr uint32_t HS = SLAB, RING0 = 5 * SLAB;                           // axis 0: half slot, ring
+    const uint32_t wave_off = opE * SLAB + sub_off;                           // ... inside a ring slot
     const int F = opE ? Kf : Cf;                                              // row length (axis 1) / row count (axis 0) of my operand
     const int my_piece0 = (lane % PPR) ^ ((d_row0 >> 2) & 3);                 // axis 0: the source piece of my 16 bytes (the same for all my instructions: RPI = 16)
     // ---- fragment geometry.  axis 1 (see bsmm_updat_tr.h): 16-lane group g16 -> features 16*(g16&1).., K half h.
@@ -346,14 +290,12 @@ updat32_a1_v2_kernel(PtrList8 Xs, PtrList8 Es, typename DT::T* __restrict__ DW, 
             aoff[0] = frag_row + (int)((meta >> 8) & 15) * (32 * ROWB);
             aoff[1] = frag_row + (int)((meta >> 12) & 15) * (32 * ROWB);
 #pragma unroll
-            for (int j = 0; j < U2_SLOTS; ++j) boff[j] = (FIVE ? 0 : SLAB) + frag_row + (int)((meta >> (16 + 4 * j)) & 15) * (32 * ROWB);
+            for (int j = 0; j < U2_SLOTS; ++j) boff[j] = SLAB + frag_row + (int)((meta >> (16 + 4 * j)) & 15) * (32 * ROWB);
         }
 
         f32x16 acc[U2_SLOTS];
 #pragma unroll
-        for (int j = 0; j < U2_SLOTS; ++j)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[j][i] = 0.f;
+        for (int j = 0; j < U2_SLOTS; ++j) zero_tile(acc[j]);
 
         // ---- DMA issue.  Issue k (k = 0 .. cnt + U2_AHEAD - 1; the first U2_AHEAD prime the ring, one more per interval) fetches
         //      chunk min(k, cnt - 1) of the range into ring slot k % U2_D: exactly NI instructions per wave every time, so one
@@ -384,19 +326,10 @@ updat32_a1_v2_kernel(PtrList8 Xs, PtrList8 Es, typename DT::T* __restrict__ DW, 
 #endif
                 if constexpr (AXIS == 1) {
                     slot += ks * 16 * ROWB;
-                    {
-                        const uint2 lo = ds_tr16(slot + aoff[0]), hi = ds_tr16(slot + aoff[0] + 4 * ROWB);
-                        a0 = make_uint4(lo.x, lo.y, hi.x, hi.y);
-                    }
-                    if constexpr (N1 > 0) {
-                        const uint2 lo = ds_tr16(slot + aoff[1]), hi = ds_tr16(slot + aoff[1] + 4 * ROWB);
-                        a1 = make_uint4(lo.x, lo.y, hi.x, hi.y);
-                    }
+                    a0 = ds_tr16_frag(slot + aoff[0], ROWB);
+                    if constexpr (N1 > 0) a1 = ds_tr16_frag(slot + aoff[1], ROWB);
 #pragma unroll
-                    for (int j = 0; j < N0 + N1; ++j) {
-                        const uint2 lo = ds_tr16(slot + boff[j]), hi = ds_tr16(slot + boff[j] + 4 * ROWB);
-                        b[j] = make_uint4(lo.x, lo.y, hi.x, hi.y);
-                    }
+                    for (int j = 0; j < N0 + N1; ++j) b[j] = ds_tr16_frag(slot + boff[j], ROWB);
                 } else {                          // K-step ks = pieces 2 ks + h of the row: the swizzled offset XOR 32 ks
                     a0 = *reinterpret_cast<const uint4*>(slot + (aoff[0] ^ (ks << 5)));
                     if constexpr (N1 > 0) a1 = *reinterpret_cast<const uint4*>(slot + (aoff[1] ^ (ks << 5)));
@@ -429,7 +362,7 @@ updat32_a1_v2_kernel(PtrList8 Xs, PtrList8 Es, typename DT::T* __restrict__ DW, 
         const int kk_ = min(k_issue, cnt - 1);                                                                               \
         const int g_ = r0 + kk_, p_ = __builtin_amdgcn_readfirstlane(g_ / nchunks), q_ = g_ - p_ * nchunks;                  \
         fb = static_cast<const unsigned char*>(uniform_ptr(opE ? pick_ptr(Es, p_) : pick_ptr(Xs, p_)));                      \
-        const uint32_t dst_ = __builtin_amdgcn_readfirstlane(base_addr + wave_off + (!FIVE ? (uint32_t)(k_issue & (D - 1)) * SLOT : (uint32_t)((2 * k_issue + opE) % 5) * HS)); \
+        const uint32_t dst_ = __builtin_amdgcn_readfirstlane(base_addr + wave_off + (uint32_t)(k_issue & (D - 1)) * SLOT);              \
         uint32_t row_off_, sub0_, sub1_, sub2_, sub3_;                                                                       \
         if constexpr (AXIS == 1) {      /* rows past N re-read row N - 1 */                                                  \
             row_off_ = (uint32_t)(q_ * CH * F) * 2u;                                                                         \
@@ -475,49 +408,41 @@ updat32_a1_v2_kernel(PtrList8 Xs, PtrList8 Es, typename DT::T* __restrict__ DW, 
         } else {                                                                                                             \
             U2_ISSUE_SLOW();                                                                                                 \
         }                                                                                                                    \
-        if constexpr (!FIVE) doff = (doff + SLOT) & (D * SLOT - 1);                                                      \
-        else { doff += 2 * HS; if (doff >= RING0) doff -= RING0; }                                                           \
+        doff = (doff + SLOT) & (D * SLOT - 1);                                                                               \
     } while (0)
             k_issue = 0; reg_left = 0;
-            if constexpr (!FIVE) {
 #pragma unroll
-                for (int d = 0; d < AHEAD; ++d) U2_ISSUE_SLOW();
-            } else {                                                // X runs two chunks ahead, DY one
-                U2_ISSUE_SLOW();
-                if (!opE) U2_ISSUE_SLOW();
-            }
-            uint32_t vslot = !FIVE ? 0u : (uint32_t)HS;         // axis 1: ring offset of the chunk; axis 0: of its DY slab (vslot0: its X slab)
-            uint32_t vslot0 = 0;
-            asm volatile("" : "+v"(vslot), "+v"(vslot0));           // the ring offsets of the fragment reads live on the vector ALU
-            uint32_t doff = !FIVE ? (uint32_t)AHEAD * SLOT : (uint32_t)((2 * k_issue + opE) % 5) * HS;   // ring offset of the next DMA destination
+            for (int d = 0; d < AHEAD; ++d) U2_ISSUE_SLOW();
+            uint32_t vslot = 0u;                                    // ring offset of the chunk
+            uint32_t vspare = 0u;                                   // (a second register the five-half-slot ring used; nothing reads it.  Without
+                                                                    //  it the specialisations are one v_mov shorter each and the loops sit 88 bytes
+                                                                    //  lower: 93.4 - 94.6 against 91.8 - 93.2 us at the bench shape, outside the
+                                                                    //  parent's range -- profiles/device_prims_ab.md.  Kept so the code is the same.)
+            asm volatile("" : "+v"(vslot), "+v"(vspare));           // the ring offset of the fragment reads lives on the vector ALU
+            uint32_t doff = (uint32_t)AHEAD * SLOT;                 // ring offset of the next DMA destination
             const uint32_t ring_base = __builtin_amdgcn_readfirstlane(base_addr + wave_off);
             int cq = __builtin_amdgcn_readfirstlane(r0 - (r0 / nchunks) * nchunks);   // chunk-in-pair index of the compute cursor (ragged N only)
 #pragma unroll 1
             for (int i = 0; i < cnt; ++i) {
-                if constexpr (!FIVE) {
-                    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NI * AHEAD - NI) : "memory");  // my share of chunk i has landed
-                } else {                           // (an X wave's latest request is chunk i + 1's)
-                    if (opE) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    else     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NI) : "memory");
-                }
+                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NI * AHEAD - NI) : "memory");      // my share of chunk i has landed
                 if (nfull != nchunks) {            // ragged N: is chunk i the last chunk of its pair?  zero its rows / columns >= N
                     if (cq == nfull) {
 #pragma unroll
                         for (int e = 0; e < NI; ++e)
                             if (AXIS == 1 ? (cq * CH + row_of(e) >= N) : (cq * CH + my_piece0 * 8 >= N))
-                                *reinterpret_cast<uint4*>(smem + (!FIVE ? (uint32_t)(i & (D - 1)) * SLOT : (uint32_t)((2 * i + opE) % 5) * HS) + wave_off + e * 1024 + lane * 16) = zero_u4();
+                                *reinterpret_cast<uint4*>(smem + (uint32_t)(i & (D - 1)) * SLOT + wave_off + e * 1024 + lane * 16) = zero_u4();
                         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                     }
                     if (++cq == nchunks) cq = 0;
                 }
                 // (two-slot ring: the slot refilled in this interval is the one set B read at the END of the previous interval --
                 //  those reads must have returned before anyone may request the refill)
-                if constexpr ((D == 2 || FIVE) && SETB) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                if constexpr (D == 2 && SETB) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #ifndef U2_NO_BARRIER
                 __builtin_amdgcn_s_barrier();                                               // everyone's has
 #endif
-                const unsigned char* slot = smem + (!FIVE ? vslot : vslot0);      // X fragments
-                const unsigned char* slot_y = smem + vslot;                           // DY fragments (axis 1: boff holds the slab offset)
+                const unsigned char* slot = smem + vslot;                                   // X fragments
+                const unsigned char* slot_y = smem + vslot;                                 // DY fragments (boff holds the slab offset)
                 if constexpr (N0 == 0) {
                     U2_ISSUE();
                 } else if constexpr (!SETB) {
@@ -534,12 +459,7 @@ updat32_a1_v2_kernel(PtrList8 Xs, PtrList8 Es, typename DT::T* __restrict__ DW, 
                     for (int ks = 0; ks < KS - 1; ++ks) { read_frags(slot, slot_y, ks); multiply(); }
                     read_frags(slot, slot_y, KS - 1);
                 }
-                if constexpr (!FIVE) {
-                    vslot = (vslot + SLOT) & (D * SLOT - 1);
-                } else {
-                    vslot += 2 * HS;  vslot = vslot >= RING0 ? vslot - RING0 : vslot;
-                    vslot0 += 2 * HS; vslot0 = vslot0 >= RING0 ? vslot0 - RING0 : vslot0;
-                }
+                vslot = (vslot + SLOT) & (D * SLOT - 1);
             }
 #undef U2_ISSUE
 #undef U2_ISSUE_SLOW

@@ -25,7 +25,6 @@
 
 #include "bsmm_common.h"
 #include "bsmm_plan.h"
-#include "bsmm_updat_tr.h"
 
 namespace bsmm {
 
@@ -67,7 +66,7 @@ updat16_win_kernel(PtrList8 Xs, PtrList8 Es, typename DT::T* __restrict__ DW, fl
     if (plan[0] != UPLAN_MAGIC || plan[1] != UPLAN_VERSION || plan[2] != UW16 || plan[3] != UP16_MAXB || plan[7] != UP_WAVES) return;
     const int32_t* item = plan + plan[6] + (size_t)blockIdx.x * UP16_ITEM;
     const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wave = wave_id();
     const int c0 = item[0], k0 = item[1];   // window origin in 16-feature blocks
     if (item[2] == 0) return;
     const int nslots = item[3] & 0xffff;
@@ -170,10 +169,8 @@ updat16_win_kernel(PtrList8 Xs, PtrList8 Es, typename DT::T* __restrict__ DW, fl
                         if constexpr (AXIS == 1) {
                             const unsigned char* sa = slot + (32 * ks + 8 * q) * UWN_ROWB + aoff[j];
                             const unsigned char* sb = slot + (32 * ks + 8 * q) * UWN_ROWB + boff[j];
-                            const uint2 a0 = ds_tr16(sa), a1 = ds_tr16(sa + 4 * UWN_ROWB);
-                            const uint2 b0 = ds_tr16(sb), b1 = ds_tr16(sb + 4 * UWN_ROWB);
-                            a[j] = make_uint4(a0.x, a0.y, a1.x, a1.y);
-                            b[j] = make_uint4(b0.x, b0.y, b1.x, b1.y);
+                            a[j] = ds_tr16_frag(sa, UWN_ROWB);
+                            b[j] = ds_tr16_frag(sb, UWN_ROWB);
                         } else {
                             const int po = ((4 * ks + q) ^ fsw) << 4;
                             a[j] = *reinterpret_cast<const uint4*>(slot + aoff[j] + po);

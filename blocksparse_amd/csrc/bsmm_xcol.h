@@ -19,7 +19,6 @@
 #include "bsmm_common.h"
 #include "bsmm_plan.h"
 #include "bsmm_xprop.h"   // XMap
-#include "bsmm_updat_tr.h"
 
 namespace bsmm {
 
@@ -72,7 +71,7 @@ xcol32_a1_kernel(const typename DT::T* __restrict__ X, const typename DT::T* __r
     const int step_off = gh.x, nsteps = gh.y, ob0 = gh.z, nob = gh.w;
     const int32_t* pairs = plan + plan[6] + step_off;
     const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wave = wave_id();
     constexpr int NI = XC_SLAB / 1024 / G;      // DMA instructions per wave per slab
     constexpr int RING = 2 * PH;
     constexpr int ROWB = G * 64;                // bytes per row of the epilogue staging tile
@@ -114,7 +113,7 @@ xcol32_a1_kernel(const typename DT::T* __restrict__ X, const typename DT::T* __r
 #pragma unroll
     for (int t = 0; t < XC_RT; ++t)
 #pragma unroll
-        for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
+        for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;   // (spelled out: zero_tile() changes this kernel's instruction order, profiles/device_prims_isa.md)
 
     auto load_w = [&](int w, Frag32<DT>& f) {
         if (w >= 0) {
@@ -209,8 +208,8 @@ xcol32_a1_kernel(const typename DT::T* __restrict__ X, const typename DT::T* __r
             const int n = t * 32 + r;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                uint32_t lo = (uint32_t)DT::from_f32(acc[t][4 * q + 0]) | ((uint32_t)DT::from_f32(acc[t][4 * q + 1]) << 16);
-                uint32_t hi = (uint32_t)DT::from_f32(acc[t][4 * q + 2]) | ((uint32_t)DT::from_f32(acc[t][4 * q + 3]) << 16);
+                uint32_t lo = pack_pair<DT>(acc[t][4 * q + 0], acc[t][4 * q + 1]);
+                uint32_t hi = pack_pair<DT>(acc[t][4 * q + 2], acc[t][4 * q + 3]);
                 const int piece = wave * 4 + q;                     // 16-byte piece inside the 512-byte row: o = 8q + 4h + ...
                 *reinterpret_cast<uint2*>(smem + n * ROWB + ((piece ^ (n & 31)) << 4) + 8 * h) = make_uint2(lo, hi);
             }
@@ -256,7 +255,7 @@ xcol32_a0_kernel(const typename DT::T* __restrict__ X, const typename DT::T* __r
     const int step_off = gh.x, nsteps = gh.y, ob0 = gh.z, nob = gh.w;
     const int32_t* pairs = plan + plan[6] + step_off;
     const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wave = wave_id();
     constexpr int NI = XC0_SLAB / 1024 / G;     // DMA instructions per wave per slab
     constexpr int RING = 2 * PH;
     static_assert(NI >= 1 && 64 % RING == 0, "slab split / ring must divide the 64-step table batch");
@@ -290,9 +289,7 @@ xcol32_a0_kernel(const typename DT::T* __restrict__ X, const typename DT::T* __r
 
     f32x16 acc[XC_RT];
 #pragma unroll
-    for (int t = 0; t < XC_RT; ++t)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
+    for (int t = 0; t < XC_RT; ++t) zero_tile(acc[t]);
 
     auto load_w = [&](int w, Frag32<DT>& f) {
         if (w >= 0) {
@@ -310,8 +307,7 @@ xcol32_a0_kernel(const typename DT::T* __restrict__ X, const typename DT::T* __r
                 const int row0 = 32 * half + 16 * kk + 8 * (g16 >> 1) + trow;
                 const int byte = 64 * t + tcolb;                                  // byte inside the row (before swizzle)
                 const int sw = (((byte >> 4) ^ (4 * trow)) << 4) | (byte & 15);
-                const uint2 lo = ds_tr16(slab + row0 * XC0_ROWB + sw), hi = ds_tr16(slab + (row0 + 4) * XC0_ROWB + sw);
-                xf[t][kk] = make_uint4(lo.x, lo.y, hi.x, hi.y);
+                xf[t][kk] = ds_tr16_frag(slab + row0 * XC0_ROWB + sw, XC0_ROWB);
             }
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk)

@@ -19,9 +19,7 @@
 #pragma once
 #include "bsmm_common.h"
 #include "bsmm_plan.h"
-#include "bsmm_updat_v2.h"   // glds16_saddr, uniform_ptr
-#include "bsmm_xcol.h"       // slab geometry
-#include "bsmm_xcol.h"
+#include "bsmm_xcol.h"       // slab geometry: XC_R, XC_SLAB, XC0_ROWB
 // row tiles whose X fragments the K = 32 pair loop holds in registers at once (measured on the retired round-1 kernel and kept: 2 on
 // feature axis 1, 1 on axis 0 where the transposing LDS reads take longer; all 8 tiles = 156 VGPRs halved the occupancy)
 #ifndef BSMM_XC16_TH_A1
@@ -59,8 +57,8 @@ __device__ __forceinline__ void x7_epilogue(f32x4 (&acc)[2][8], unsigned char* s
 #pragma unroll
             for (int tt = 0; tt < 8; ++tt) {
                 const int n = 16 * tt + o16;
-                const uint32_t lo = (uint32_t)DT::from_f32(acc[c][tt][0]) | ((uint32_t)DT::from_f32(acc[c][tt][1]) << 16);
-                const uint32_t hi = (uint32_t)DT::from_f32(acc[c][tt][2]) | ((uint32_t)DT::from_f32(acc[c][tt][3]) << 16);
+                const uint32_t lo = pack_pair<DT>(acc[c][tt][0], acc[c][tt][1]);
+                const uint32_t hi = pack_pair<DT>(acc[c][tt][2], acc[c][tt][3]);
                 const int piece = (2 * wave + c) * 2 + (q >> 1);
                 *reinterpret_cast<uint2*>(smem + n * ROWB + ((piece ^ (n & 31)) << 4) + 8 * (q & 1)) = make_uint2(lo, hi);
             }
@@ -110,7 +108,7 @@ xcol16_v2_kernel(const typename DT::T* __restrict__ X, const typename DT::T* __r
     const int4 gh = *reinterpret_cast<const int4*>(plan + plan[5] + 4 * grp);
     const int ph_off = __builtin_amdgcn_readfirstlane(gh.x), nph = __builtin_amdgcn_readfirstlane(gh.y);
     const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wave = wave_id();
     const int32_t* pxt = plan + plan[6] + ph_off;
     const int4* tab = reinterpret_cast<const int4*>(plan + plan[7]) + ((size_t)ph_off * 16 + wave) * 3;   // X7_ROW = 12 words
     const int o16 = lane & 15, q = lane >> 4;
@@ -150,8 +148,7 @@ xcol16_v2_kernel(const typename DT::T* __restrict__ X, const typename DT::T* __r
             const int row0 = 32 * ks + 8 * q + trow;
             const int byte = (16 * tt + 4 * (t16 & 3)) * 2;
             const int sw = (((byte >> 4) ^ (4 * trow)) << 4) | (byte & 15);
-            const uint2 lo = ds_tr16(slab + row0 * XC0_ROWB + sw), hi = ds_tr16(slab + (row0 + 4) * XC0_ROWB + sw);
-            return make_uint4(lo.x, lo.y, hi.x, hi.y);
+            return ds_tr16_frag(slab + row0 * XC0_ROWB + sw, XC0_ROWB);
         }
     };
     // ... of ONE block of the K-step (hf = 0 / 1: features 32 ks + 16 hf .. + 16) for the K = 16 instruction: lane (n, q) holds
@@ -408,7 +405,7 @@ xcol16_list_kernel(const typename DT::T* __restrict__ X, const typename DT::T* _
     const int4 gh = *reinterpret_cast<const int4*>(plan + plan[5] + 4 * grp);
     const int ph_off = __builtin_amdgcn_readfirstlane(gh.x), nph = __builtin_amdgcn_readfirstlane(gh.y);
     const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wave = wave_id();
     // list section of my group: per phase X7_PHW words = [16 waves][X7_LIST] block lists, [64][2] request table
     const unsigned char* sect = static_cast<const unsigned char*>(uniform_ptr(plan + plan[11] + (size_t)ph_off * X7_PHW));
     const uint32_t llane = (uint32_t)(wave * X7_LIST + min(lane, X7_LIST - 1)) * 4u;    // my word of my list row (lanes 0..39 are read)
@@ -543,39 +540,9 @@ xcol16_list_kernel(const typename DT::T* __restrict__ X, const typename DT::T* _
                 const int n0 = cnt & 0xff, n1 = (cnt >> 8) & 0xff;
 #endif
                 if (n0 + n1 > 0) {
-#ifdef X7L_FULL_AHEAD
-                    // one block ahead: the 9 fragment reads of block e + 1 are issued before the 8 MFMAs of block e, two register sets
-                    const uint32_t xlh = xl ^ (uint32_t)(hb << 15), wlh = wl + (uint32_t)(hb * X7_WHALF);
-                    uint2 wA, wB, fA[8], fB[8];
-#define X7_FETCH(W_, F_, e_)                                                                                                     \
-    do {                                                                                                                         \
-        const uint32_t sx_ = (uint32_t)__builtin_amdgcn_readlane(lcur, 2 * (e_)) & XMASK, sw_ = (uint32_t)__builtin_amdgcn_readlane(lcur, 2 * (e_) + 1); \
-        const uint32_t xa_ = xlh ^ sx_;                                                                                          \
-        W_ = wread(wlh + sw_);                                                                  \
-        _Pragma("unroll") for (int t = 0; t < 8; ++t) F_[t] = xread(xa_, t);                                                     \
-    } while (0)
-#define X7_VISIT(C)                                                                                                              \
-    do {                                                                                                                         \
-        ++e;                                                                                                                     \
-        X7_FETCH(wB, fB, e);                  /* (past the end: zero words of the row's tail -- a valid address, not used) */     \
-        __builtin_amdgcn_sched_barrier(0);                                                                                       \
-        _Pragma("unroll") for (int t = 0; t < 8; ++t) acc[C][t] = DT::mfma16k16(wA, fA[t], acc[C][t]);                          \
-        __builtin_amdgcn_sched_barrier(0);                                                                                       \
-        wA = wB;                                                                                                                 \
-        _Pragma("unroll") for (int t = 0; t < 8; ++t) fA[t] = fB[t];                                                             \
-    } while (0)
-                    X7_FETCH(wA, fA, 0);
-                    int e = 0;
-#pragma unroll 1
-                    for (int k = 0; k < n0; ++k) X7_VISIT(0);
-#pragma unroll 1
-                    for (int k = 0; k < n1; ++k) X7_VISIT(1);
-#undef X7_VISIT
-#undef X7_FETCH
-#else
                     // software pipeline in halves of 4 row tiles: [reads tiles 4-7 of e] [4 MFMAs tiles 0-3] [reads weights and tiles 0-3 of
-                    // e + 1] [4 MFMAs tiles 4-7].  (Measured: fetching the whole next block ahead -- X7L_FULL_AHEAD, two register sets and 9
-                    // 64-bit moves per block -- is slower, 91 against 81 us.)
+                    // e + 1] [4 MFMAs tiles 4-7].  (Measured: fetching the whole next block ahead -- two register sets and 9
+                    // 64-bit moves per block -- is slower, 91 against 81 us; profiles/r03_x7_README.md.)
                     const uint32_t xlh = xl ^ (uint32_t)(hb << 15), wlh = wl + (uint32_t)(hb * X7_WHALF);
                     int e = 0;
                     uint2 w, xA[4], xB[4];
@@ -625,7 +592,6 @@ xcol16_list_kernel(const typename DT::T* __restrict__ X, const typename DT::T* _
 #undef X7_VISIT
 #undef X7L_XREAD
 #undef X7L_MFMA
-#endif
                 }
             X7L_STAMP(4);
             hb ^= 1;

@@ -17,7 +17,6 @@
 #pragma once
 #include "bsmm_common.h"
 #include "bsmm_plan.h"
-#include "bsmm_updat_v2.h"   // glds16_saddr, uniform_ptr
 #include "bsmm_xprop.h"      // XMap
 
 namespace bsmm {
@@ -37,12 +36,6 @@ namespace bsmm {
 #endif
 #ifndef X2_NO_EPILOGUE
 #define X2_NO_EPILOGUE 0
-#endif
-#ifndef X2_READS_FIRST
-#define X2_READS_FIRST 0     // 1: all ten fragment reads of a block before its first MFMA
-#endif
-#ifndef X2_LATE_ISSUE
-#define X2_LATE_ISSUE 0      // 1: odd waves request the next phase AFTER their blocks
 #endif
 constexpr int X2_R = 128;                          // minibatch rows per workgroup
 constexpr int X2_SLAB = X2_R * 128;                // 16 KiB
@@ -80,7 +73,7 @@ xcol32_v2_kernel(const typename DT::T* __restrict__ X, const typename DT::T* __r
     const int ph_off = __builtin_amdgcn_readfirstlane(gh.x), nph = __builtin_amdgcn_readfirstlane(gh.y);
     const int ob0 = __builtin_amdgcn_readfirstlane(gh.z), nob = __builtin_amdgcn_readfirstlane(gh.w);
     const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (spelled out: wave_id() changes this kernel's instruction order, profiles/device_prims_isa.md)
     const int32_t* pxt = plan + plan[6] + 2 * ph_off;                                                   // two words per phase
     const int4* tab = reinterpret_cast<const int4*>(plan + plan[7]) + ((size_t)ph_off * X2_G + wave) * 2;   // X2_ROW = 8 words
     const int r = lane & 31, h = lane >> 5;
@@ -137,9 +130,7 @@ xcol32_v2_kernel(const typename DT::T* __restrict__ X, const typename DT::T* __r
 
     f32x16 acc[4];
 #pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
+    for (int t = 0; t < 4; ++t) zero_tile(acc[t]);
 
     // gated calls: lanes 0..2 fetch the gates of my three duties (first half block of a block only) for ring half hb_; the
     // values are written into that half's gate table at the top of the next phase, behind the same wait as the DMAs
@@ -194,12 +185,8 @@ xcol32_v2_kernel(const typename DT::T* __restrict__ X, const typename DT::T* __r
         uint4 wq[2];
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
-            if constexpr (TRANSW) {
-                const uint2 lo = ds_tr16(smem + wrd[kk] + woff), hi = ds_tr16(smem + wrd[kk] + woff + 4 * 64);
-                wq[kk] = make_uint4(lo.x, lo.y, hi.x, hi.y);
-            } else {
-                wq[kk] = *reinterpret_cast<const uint4*>(smem + wrd[kk] + woff);
-            }
+            if constexpr (TRANSW) wq[kk] = ds_tr16_frag(smem + wrd[kk] + woff, 64);
+            else                  wq[kk] = *reinterpret_cast<const uint4*>(smem + wrd[kk] + woff);
         }
         if constexpr (GATED) {
             // one K half at a time (4 activation fragments live instead of 8: the split pieces need the registers)
@@ -236,9 +223,8 @@ xcol32_v2_kernel(const typename DT::T* __restrict__ X, const typename DT::T* __r
         for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
             for (int t = 0; t < 4; ++t) xf[t][kk] = xread(t, kk);
-#if X2_READS_FIRST
-        __builtin_amdgcn_sched_barrier(0);
-#endif
+        // (all ten fragment reads of a block forced in front of its first MFMA by a sched_barrier: 61.5 / 84.0 / 158.2 us, neutral --
+        //  profiles/r02_xcol_v2_ablation.md)
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
@@ -273,8 +259,9 @@ xcol32_v2_kernel(const typename DT::T* __restrict__ X, const typename DT::T* __r
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 }
                 __builtin_amdgcn_s_barrier();                        // everyone's have; everyone left the previous phase
-                const bool late = X2_LATE_ISSUE && (wave & 1);
-                if (!late && tb + qi + 1 < nph) {
+                // (odd waves requesting the next phase AFTER their blocks: 69.5 / 86.6 / 163.3 us, worse -- with a drain per phase the late
+                //  requests lose half their time to land; profiles/r02_xcol_v2_ablation.md)
+                if (tb + qi + 1 < nph) {
                     const int px1 = __builtin_amdgcn_readlane(pxv, qi), px1b = PH > 2 ? __builtin_amdgcn_readlane(pxv2, qi) : -1;
                     const int d0 = __builtin_amdgcn_readlane(d0v, qi), d1 = __builtin_amdgcn_readlane(d1v, qi), d2 = __builtin_amdgcn_readlane(d2v, qi);
                     X2_ISSUE(px1, px1b, d0, d1, d2, hb ^ 1);
@@ -294,11 +281,6 @@ xcol32_v2_kernel(const typename DT::T* __restrict__ X, const typename DT::T* __r
                         if (((cw2 >> 16) & 0xff) != 0xff) block(xo + 3 * X2_SLAB, wo, (cw2 >> 16) & 0xff, 0);
                         if ((cw2 >> 24) != 0xff)          block(xo + 3 * X2_SLAB, wo, cw2 >> 24, 1);
                     }
-                }
-                if (late && tb + qi + 1 < nph) {
-                    const int px1 = __builtin_amdgcn_readlane(pxv, qi), px1b = PH > 2 ? __builtin_amdgcn_readlane(pxv2, qi) : -1;
-                    const int d0 = __builtin_amdgcn_readlane(d0v, qi), d1 = __builtin_amdgcn_readlane(d1v, qi), d2 = __builtin_amdgcn_readlane(d2v, qi);
-                    X2_ISSUE(px1, px1b, d0, d1, d2, hb ^ 1);
                 }
                 hb ^= 1;
             }
@@ -336,8 +318,8 @@ xcol32_v2_kernel(const typename DT::T* __restrict__ X, const typename DT::T* __r
             const int n = t * 32 + r;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const uint32_t lo = (uint32_t)DT::from_f32(acc[t][4 * q + 0]) | ((uint32_t)DT::from_f32(acc[t][4 * q + 1]) << 16);
-                const uint32_t hi = (uint32_t)DT::from_f32(acc[t][4 * q + 2]) | ((uint32_t)DT::from_f32(acc[t][4 * q + 3]) << 16);
+                const uint32_t lo = pack_pair<DT>(acc[t][4 * q + 0], acc[t][4 * q + 1]);
+                const uint32_t hi = pack_pair<DT>(acc[t][4 * q + 2], acc[t][4 * q + 3]);
                 const int piece = wave * 4 + q;
                 *reinterpret_cast<uint2*>(smem + n * ROWB + ((piece ^ (n & 31)) << 4) + 8 * h) = make_uint2(lo, hi);
             }

@@ -18,7 +18,7 @@
 #pragma once
 #include "bsmm_common.h"
 #include "bsmm_plan.h"
-#include "bsmm_xcol.h"
+#include "bsmm_xcol.h"       // slab geometry: XC_R, XC_SLAB, XC0_*
 
 namespace bsmm {
 
@@ -121,7 +121,7 @@ xcol32s_kernel(const uint16_t* __restrict__ Xp, const uint16_t* __restrict__ Wp,
     const int step_off = gh.x, nsteps = gh.y, ob0 = gh.z, nob = gh.w;
     const int32_t* pairs = plan + plan[6] + step_off;
     const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wave = wave_id();
     const int32_t* wt0 = plan + plan[7] + 2 * XS_G * step_off + (2 * wave) * nsteps;   // my column, even half of the pair
     const int32_t* wt1 = wt0 + nsteps;                                                  // odd half
     const int r = lane & 31, h = lane >> 5;
@@ -159,9 +159,7 @@ xcol32s_kernel(const uint16_t* __restrict__ Xp, const uint16_t* __restrict__ Wp,
 
     f32x16 acc[XC_RT];
 #pragma unroll
-    for (int t = 0; t < XC_RT; ++t)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
+    for (int t = 0; t < XC_RT; ++t) zero_tile(acc[t]);
 
     u32x4 wq[3][2];      // weight pieces of the entry this wave handles next: [piece][K half]
 #pragma unroll
@@ -196,10 +194,7 @@ xcol32s_kernel(const uint16_t* __restrict__ Xp, const uint16_t* __restrict__ Wp,
                     const int row0 = 32 * half + 16 * kk + 8 * (g16 >> 1) + trow;
                     const int byte = 64 * t + tcolb;
                     const unsigned char* p = slot + row0 * XC0_ROWB + ((((byte >> 4) ^ (4 * trow)) << 4) | (byte & 15));
-                    auto tr = [&](const unsigned char* q) {
-                        const uint2 lo = ds_tr16(q), hi = ds_tr16(q + 4 * XC0_ROWB);
-                        return make_uint4(lo.x, lo.y, hi.x, hi.y);
-                    };
+                    auto tr = [&](const unsigned char* q) { return ds_tr16_frag(q, XC0_ROWB); };
                     x0 = tr(p); x1 = tr(p + XC_SLAB); x2 = tr(p + 2 * XC_SLAB);
                 }
                 // smallest terms first
@@ -332,7 +327,7 @@ xcol32sf_kernel(const float* __restrict__ Xf, const uint16_t* __restrict__ Wp, f
     const int step_off = gh.x, nsteps = gh.y, ob0 = gh.z, nob = gh.w;
     const int32_t* pairs = plan + plan[6] + step_off;
     const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wave = wave_id();
     const int32_t* wt0 = plan + plan[7] + 2 * XS_G * step_off + (2 * wave) * nsteps;   // my column, even half of the pair
     const int32_t* wt1 = wt0 + nsteps;                                                  // odd half
     const int r = lane & 31, h = lane >> 5;
@@ -388,9 +383,7 @@ xcol32sf_kernel(const float* __restrict__ Xf, const uint16_t* __restrict__ Wp, f
 
     f32x16 acc[XC_RT];
 #pragma unroll
-    for (int t = 0; t < XC_RT; ++t)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
+    for (int t = 0; t < XC_RT; ++t) zero_tile(acc[t]);
 
     u32x4 wq[3][2];      // weight pieces of the entry this wave handles next: [piece][K half]
 #pragma unroll

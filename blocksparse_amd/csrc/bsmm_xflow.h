@@ -24,8 +24,6 @@
 #pragma once
 #include "bsmm_common.h"
 #include "bsmm_plan.h"
-#include "bsmm_updat_v2.h"   // glds16_saddr, uniform_ptr
-#include "bsmm_updat_tr.h"   // ds_tr16
 #include "bsmm_xprop.h"      // XMap
 
 namespace bsmm {
@@ -38,22 +36,6 @@ namespace bsmm {
 #endif
 #ifndef X4_NO_MATH
 #define X4_NO_MATH 0
-#endif
-#ifndef X4_READS_FIRST
-#define X4_READS_FIRST 1
-#endif
-#ifndef X4_PUBLISH_FIRST
-#define X4_PUBLISH_FIRST 1
-#endif
-#ifndef X4_FETCH_EARLY
-#define X4_FETCH_EARLY 0      // 1: a BLOCK event requests its wave's weight block two events ahead right behind its first MFMA instead of behind the
-                              //    block: bit-identical, measured 91.4 / 81.7 against 88.9 / 78.7 us (profiles/r05_flow_fetch_early.txt) -- not taken
-#endif
-#ifndef X4_STAGGER
-#define X4_STAGGER 0
-#endif
-#ifndef X4_PRIO
-#define X4_PRIO 0             // 1: a wave multiplying a block runs at raised issue priority (the pollers at 0)
 #endif
 #ifdef X4_TIMELINE
 // time line of workgroup 0 (debug builds): per global step [0..255]: [0..3] REQ start (after its progress poll) of part 0 / 1, then REQ
@@ -113,24 +95,6 @@ __device__ __forceinline__ void x4_poll_all_ge(uint32_t v_addr, uint32_t s_need)
 
 // the wait of a BLOCK / ANN event, chosen by the event's control word: bit 3 vmcnt(2), bit 4 vmcnt(0), else vmcnt(DI) with DI = the requests a REQ
 // of THIS kernel issues (the plan counts X4_DI per REQ; a kernel with smaller slabs issues fewer, and the wait must not assume more)
-// the activation slabs' requests with a cache policy of their own (X4_XPOL: "" default, " nt" = streaming: measured in profiles/r05_flow_cache_policy.txt)
-#ifndef X4_XPOL
-#define X4_XPOL ""
-#endif
-__device__ __forceinline__ void x4_glds_x(const void* sbase, uint32_t voff, uint32_t lds_byte_addr) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" X4_XPOL "\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_byte_addr) : "memory");
-}
-__device__ __forceinline__ void x4_glds_x4(const void* sbase, uint32_t v0, uint32_t v1, uint32_t v2, uint32_t v3, uint32_t lds_byte_addr) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %6\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %5" X4_XPOL "\n\t"
-                 "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %5" X4_XPOL "\n\t"
-                 "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, %5" X4_XPOL "\n\t"
-                 "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %4, %5" X4_XPOL "\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(v0), "v"(v1), "v"(v2), "v"(v3), "s"(sbase), "s"(lds_byte_addr) : "memory", "scc");
-}
-
 template <int DI>
 __device__ __forceinline__ void x4_wait_ctl(uint32_t ctl) {
     asm volatile("s_bitcmp1_b32 %0, 3\n\ts_cbranch_scc0 1f\n\ts_waitcnt vmcnt(2)\n\ts_branch 3f\n"
@@ -154,17 +118,14 @@ xflow32_kernel(const typename DT::T* __restrict__ X, const typename DT::T* __res
     static_assert(D * SLAB == X4_WBASE && DI % 4 == 0 && D <= 16, "flow kernel: ring geometry");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wave = wave_id();
     const int r = lane & 31, h = lane >> 5;
     const uint32_t base_addr = lds_addr_of(smem);
     const uint32_t prog_addr = base_addr + X4_FLAGS, full_addr = base_addr + X4_FLAGS + 64;
     if (threadIdx.x < 32) reinterpret_cast<uint32_t*>(smem + X4_FLAGS)[threadIdx.x] = 0u;
     __syncthreads();                                   // the only workgroup barrier of the kernel
-#if X4_STAGGER
-    // experiment: the workgroups of an XCD start X4_STAGGER x 64 cycles apart, so that the tiles that share a weight block (and the groups that
-    // share a slab) do not ask for it in the same few hundred cycles -- the followers should find it in the L2 instead of waiting for the fill
-    for (int i = ((blockIdx.x >> 3) & 31) * X4_STAGGER; i > 0; --i) __builtin_amdgcn_s_sleep(1);
-#endif
+    // (workgroup starts staggered by 64 .. 1024 cycles within an XCD, so that sharers of a weight block find it in the L2: 89.9 / 90.6 / 103 us,
+    //  no gain -- profiles/r05_README.md)
 
     const int npairs_full = Cin / 64;
     const unsigned char* xt = reinterpret_cast<const unsigned char*>(X);
@@ -222,9 +183,7 @@ xflow32_kernel(const typename DT::T* __restrict__ X, const typename DT::T* __res
 
         f32x16 acc[RT];
 #pragma unroll
-        for (int t = 0; t < RT; ++t)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
+        for (int t = 0; t < RT; ++t) zero_tile(acc[t]);
 
         uint32_t s_w = 0, s_wf = 0;  // XOR offset of the weight slot to multiply from / to fetch into (0 or 2048)
         for (int eb = 0; eb < nev; eb += 64) {
@@ -262,7 +221,6 @@ xflow32_kernel(const typename DT::T* __restrict__ X, const typename DT::T* __res
 #ifdef X4_STAMPS
                 tacc[7] += 1;
 #endif
-                bool fetched = false;
                 if (ty_s & 1) { X4_T0(); x4_wait_ctl<DI>(ctl); X4_T1(0); }     // BLOCK (1) or ANN (3): wait for my fetch / my requests
                 if (ty_s == 1) {
                     // ---- BLOCK: my weight block (fetched two BLOCK events ago) x the slab of its step ----
@@ -272,23 +230,19 @@ xflow32_kernel(const typename DT::T* __restrict__ X, const typename DT::T* __res
                     X4_TL(dbg_s, 6 + 2 * wave);
 #endif
                     X4_T0();
-                    if (X4_PRIO) __builtin_amdgcn_s_setprio(3);
+                    // (raised issue priority around a block, s_setprio 3: 85 / 79 against 87 / 79 us in the same run, profiles/r04_headline_ab.md -- not taken)
                     if (!X4_NO_MATH) {
                         const uint32_t sx = (uint32_t)__builtin_amdgcn_readlane(v_x, idx);
                         uint4 wq[2];
 #pragma unroll
                         for (int kk = 0; kk < 2; ++kk) {
-                            if constexpr (TRANSW) {
-                                const uint2 lo = ds_tr16(smem + (wrd[kk] ^ s_w)), hi = ds_tr16(smem + (wrd[kk] ^ s_w) + 4 * 64);
-                                wq[kk] = make_uint4(lo.x, lo.y, hi.x, hi.y);
-                            } else {
-                                wq[kk] = *reinterpret_cast<const uint4*>(smem + (wrd[kk] ^ s_w));
-                            }
+                            if constexpr (TRANSW) wq[kk] = ds_tr16_frag(smem + (wrd[kk] ^ s_w), 64);
+                            else                  wq[kk] = *reinterpret_cast<const uint4*>(smem + (wrd[kk] ^ s_w));
                         }
-#if X4_READS_FIRST
                         // a block is on its wave's critical path: its LATENCY counts.  Both weight fragments and the four K-half-0
                         // activation fragments are in flight before the first MFMA; each K-half-1 fragment is requested right behind
-                        // the MFMA that consumed its K-half-0 sibling (into the same registers) and lands under the other three
+                        // the MFMA that consumed its K-half-0 sibling (into the same registers) and lands under the other three.  (All reads up
+                        // front, interleaved as the compiler likes: no faster at any density, profiles/r04_headline_ab.md.)
                         uint4 xf[RT];
 #pragma unroll
                         for (int t = 0; t < RT; ++t) xf[t] = *reinterpret_cast<const uint4*>(smem + (xrd[0] ^ sx) + t * 4096);
@@ -298,34 +252,9 @@ xflow32_kernel(const typename DT::T* __restrict__ X, const typename DT::T* __res
                             acc[t] = DT::mfma32(wq[0], xf[t], acc[t]);
                             xf[t] = *reinterpret_cast<const uint4*>(smem + (xrd[1] ^ sx) + t * 4096);
                             __builtin_amdgcn_sched_barrier(0);
-#if X4_FETCH_EARLY
-                            // my weight block two BLOCK events ahead goes into the slot THIS block's fragments came from: they are in registers
-                            // once the first MFMA could issue (LDS reads return in order: its activation fragment was requested behind them), so
-                            // the two requests are issued here, under the matrix work, instead of behind the block on the wave's critical path
-                            // (the order of the wave's vector-memory operations, hence every vmcnt of the plan, is unchanged)
-                            if (t == 0 && (ctl & 64u)) {
-                                if (!X4_NO_WDMA) {
-                                    const uint32_t fo = (uint32_t)__builtin_amdgcn_readlane(v_fw, idx);
-                                    glds16_saddr_x2(wsel, wvoff + fo, wvoff + fo + 1024u, base_addr + (wslot0 ^ s_wf));
-                                }
-                                s_wf ^= 2048u;
-                                fetched = true;
-                            }
-#endif
                         }
 #pragma unroll
                         for (int t = 0; t < RT; ++t) acc[t] = DT::mfma32(wq[1], xf[t], acc[t]);
-#else
-                        uint4 xf[RT][2];
-#pragma unroll
-                        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-                            for (int t = 0; t < RT; ++t) xf[t][kk] = *reinterpret_cast<const uint4*>(smem + (xrd[kk] ^ sx) + t * 4096);
-#pragma unroll
-                        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-                            for (int t = 0; t < RT; ++t) acc[t] = DT::mfma32(wq[kk], xf[t][kk], acc[t]);
-#endif
                     }
                     s_w ^= 2048u;
 #ifdef X4_STAMPS
@@ -345,6 +274,7 @@ xflow32_kernel(const typename DT::T* __restrict__ X, const typename DT::T* __res
                     const uint32_t dbg_r = (uint32_t)__builtin_amdgcn_readlane(v_dbg, idx);
                     X4_TL(dbg_r & 0xffff, dbg_r >> 16);
 #endif
+                    // (a non-temporal policy on these requests did not pay: profiles/r05_flow_cache_policy.txt)
                     if (!X4_NO_XDMA) {
                         const uint32_t dst = base_addr + (uint32_t)__builtin_amdgcn_readlane(v_x, idx);
                         const uint32_t poff = (uint32_t)__builtin_amdgcn_readlane(v_fa, idx);
@@ -355,8 +285,8 @@ xflow32_kernel(const typename DT::T* __restrict__ X, const typename DT::T* __res
                             const uint32_t vo_o = (pc_e & 4u) ? vo_e - 64u : vo_e + 64u;
 #pragma unroll
                             for (int k = 0; k < DI; k += 4)
-                                x4_glds_x4(xtile, vo_e + (k0 + (k + 0) * stride16), vo_o + (k0 + (k + 1) * stride16), vo_e + (k0 + (k + 2) * stride16),
-                                                vo_o + (k0 + (k + 3) * stride16), dst + k * 1024);
+                                glds16_saddr_x4(xtile, vo_e + (k0 + (k + 0) * stride16), vo_o + (k0 + (k + 1) * stride16), vo_e + (k0 + (k + 2) * stride16),
+                                                     vo_o + (k0 + (k + 3) * stride16), dst + k * 1024);
                         } else {
                             const bool tail = (int)(poff >> 7) >= npairs_full;
 #pragma unroll
@@ -366,7 +296,7 @@ xflow32_kernel(const typename DT::T* __restrict__ X, const typename DT::T* __res
                                 const int piece = (lane & 7) ^ ((row >> 1) & 7);
                                 uint32_t voff = (uint32_t)xr * (uint32_t)Cin * 2u + piece * 16 + poff;
                                 if (tail && (piece & 4)) voff -= 64;                 // last pair of an odd block count: re-read its even half
-                                x4_glds_x(xtile, voff, dst + k * 1024);
+                                glds16_saddr(xtile, voff, dst + k * 1024);
                             }
                         }
                     }
@@ -383,17 +313,18 @@ xflow32_kernel(const typename DT::T* __restrict__ X, const typename DT::T* __res
                 }
                 if (ty_s < 2) {
                     // ---- after a BLOCK / NOP: my next weight fetch (into the slot the block just freed), my progress ----
+                    // (the fetch right behind the block's first MFMA instead: bit-identical, 91.4 / 81.7 against 88.9 / 78.7 us,
+                    //  profiles/r05_flow_fetch_early.txt -- not taken)
                     X4_T0();
-                    if (X4_PUBLISH_FIRST) x4_lane_write(em, my_prog_s, v_pv);   // (first: the requesters of the slot I just left are waiting for this)
-                    if ((ctl & 64u) && !fetched) {
+                    x4_lane_write(em, my_prog_s, v_pv);   // (first: the requesters of the slot I just left are waiting for this; after the fetch
+                                                          //  it measured the same, profiles/r04_headline_ab.md)
+                    if (ctl & 64u) {
                         if (!X4_NO_WDMA) {
                             const uint32_t fo = (uint32_t)__builtin_amdgcn_readlane(v_fw, idx);
                             glds16_saddr_x2(wsel, wvoff + fo, wvoff + fo + 1024u, base_addr + (wslot0 ^ s_wf));
                         }
                         s_wf ^= 2048u;
                     }
-                    if (!X4_PUBLISH_FIRST) x4_lane_write(em, my_prog_s, v_pv);
-                    if (X4_PRIO) __builtin_amdgcn_s_setprio(0);
                     X4_T1(5);
                 }
             }
@@ -414,8 +345,8 @@ xflow32_kernel(const typename DT::T* __restrict__ X, const typename DT::T* __res
                     const int n = tt * 32 + r;
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
-                        const uint32_t lo = (uint32_t)DT::from_f32(acc[t][4 * q + 0]) | ((uint32_t)DT::from_f32(acc[t][4 * q + 1]) << 16);
-                        const uint32_t hi = (uint32_t)DT::from_f32(acc[t][4 * q + 2]) | ((uint32_t)DT::from_f32(acc[t][4 * q + 3]) << 16);
+                        const uint32_t lo = pack_pair<DT>(acc[t][4 * q + 0], acc[t][4 * q + 1]);
+                        const uint32_t hi = pack_pair<DT>(acc[t][4 * q + 2], acc[t][4 * q + 3]);
                         *reinterpret_cast<uint2*>(stage + n * 64 + ((q ^ ((n >> 2) & 3)) << 4) + 8 * h) = make_uint2(lo, hi);
                     }
                 }

@@ -16,8 +16,6 @@
 // Sums are formed in lut order, one fp32 accumulator per output: bit-identical to the staged / flow kernels.
 #pragma once
 #include "bsmm_common.h"
-#include "bsmm_updat_tr.h"   // ds_tr16
-#include "bsmm_updat_v2.h"   // glds16_saddr_x2 / _x4, uniform_ptr
 #include "bsmm_xprop.h"      // XMap
 
 namespace bsmm {
@@ -43,7 +41,7 @@ xmid32_kernel(const typename DT::T* __restrict__ X, const typename DT::T* __rest
     constexpr int WRING = XMD_DX * XT;                                // byte offset of the weight ring inside the wave's LDS
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wave = wave_id();
     // by_column = 0: the workgroup's waves take four consecutive output blocks and the same rows (map: row chunks x block quads);
     // by_column = 1: one output block and four consecutive row chunks (map: chunk quads x blocks) -- the waves share the weight blocks in
     // the L1; right while the whole activation matrix fits an XCD's L2 next to the weights
@@ -87,9 +85,7 @@ xmid32_kernel(const typename DT::T* __restrict__ X, const typename DT::T* __rest
 
     f32x16 acc[RT];
 #pragma unroll
-    for (int t = 0; t < RT; ++t)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
+    for (int t = 0; t < RT; ++t) zero_tile(acc[t]);
 
     // the entry list, lane-resident in chunks of 64 (one vector load instead of a scalar load chain per entry)
     for (int eb = 0; eb < cnt; eb += 64) {
@@ -134,12 +130,8 @@ xmid32_kernel(const typename DT::T* __restrict__ X, const typename DT::T* __rest
             uint4 wq[2], xf[RT][2];
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk) {
-                if constexpr (TRANSW) {
-                    const uint2 lo = ds_tr16(sw + wrd[kk]), hi = ds_tr16(sw + wrd[kk] + 4 * 64);
-                    wq[kk] = make_uint4(lo.x, lo.y, hi.x, hi.y);
-                } else {
-                    wq[kk] = *reinterpret_cast<const uint4*>(sw + wrd[kk]);
-                }
+                if constexpr (TRANSW) wq[kk] = ds_tr16_frag(sw + wrd[kk], 64);
+                else                  wq[kk] = *reinterpret_cast<const uint4*>(sw + wrd[kk]);
 #pragma unroll
                 for (int t = 0; t < RT; ++t) xf[t][kk] = *reinterpret_cast<const uint4*>(sx + xrd[kk] + t * 2048);
             }
@@ -165,8 +157,8 @@ xmid32_kernel(const typename DT::T* __restrict__ X, const typename DT::T* __rest
             const int t = 2 * pass + tt, n = tt * 32 + r;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const uint32_t lo = (uint32_t)DT::from_f32(acc[t][4 * q + 0]) | ((uint32_t)DT::from_f32(acc[t][4 * q + 1]) << 16);
-                const uint32_t hi = (uint32_t)DT::from_f32(acc[t][4 * q + 2]) | ((uint32_t)DT::from_f32(acc[t][4 * q + 3]) << 16);
+                const uint32_t lo = pack_pair<DT>(acc[t][4 * q + 0], acc[t][4 * q + 1]);
+                const uint32_t hi = pack_pair<DT>(acc[t][4 * q + 2], acc[t][4 * q + 3]);
                 *reinterpret_cast<uint2*>(ring + pass * 4096 + n * 64 + ((q ^ ((n >> 2) & 3)) << 4) + 8 * h) = make_uint2(lo, hi);
             }
         }

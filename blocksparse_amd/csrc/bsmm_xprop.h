@@ -87,9 +87,7 @@ xprop32_kernel(const typename DT::T* __restrict__ X, const typename DT::T* __res
 
     f32x16 acc[NSUB];
 #pragma unroll
-    for (int s = 0; s < NSUB; ++s)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[s][i] = 0.f;
+    for (int s = 0; s < NSUB; ++s) zero_tile(acc[s]);
 
     for (int e = 0; e < cnt; ++e) {
         const int2 cw = ent[e];
@@ -112,8 +110,7 @@ xprop32_kernel(const typename DT::T* __restrict__ X, const typename DT::T* __res
             }
             if constexpr (GATED) {
                 f32x16 t;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) t[i] = 0.f;
+                zero_tile(t);
                 mma32<DT>(wf, xf, t);
 #pragma unroll
                 for (int i = 0; i < 16; ++i) acc[s][i] = fmaf(g, t[i], acc[s][i]);
@@ -133,8 +130,8 @@ xprop32_kernel(const typename DT::T* __restrict__ X, const typename DT::T* __res
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     if constexpr (DT::is16) {
-                        uint32_t lo = (uint32_t)DT::from_f32(acc[s][4 * g + 0]) | ((uint32_t)DT::from_f32(acc[s][4 * g + 1]) << 16);
-                        uint32_t hi = (uint32_t)DT::from_f32(acc[s][4 * g + 2]) | ((uint32_t)DT::from_f32(acc[s][4 * g + 3]) << 16);
+                        uint32_t lo = pack_pair<DT>(acc[s][4 * g + 0], acc[s][4 * g + 1]);
+                        uint32_t hi = pack_pair<DT>(acc[s][4 * g + 2], acc[s][4 * g + 3]);
                         *reinterpret_cast<uint2*>(yrow + 8 * g) = make_uint2(lo, hi);
                     } else {
                         *reinterpret_cast<float4*>(yrow + 8 * g) =
@@ -269,8 +266,8 @@ xprop16_kernel(const typename DT::T* __restrict__ X, const typename DT::T* __res
             if constexpr (AXIS == 1) {
                 T* yp = Y + (size_t)n * Kout + ob * 16 + 4 * q;
                 if constexpr (DT::is16) {
-                    uint32_t lo = (uint32_t)DT::from_f32(acc[s][0]) | ((uint32_t)DT::from_f32(acc[s][1]) << 16);
-                    uint32_t hi = (uint32_t)DT::from_f32(acc[s][2]) | ((uint32_t)DT::from_f32(acc[s][3]) << 16);
+                    uint32_t lo = pack_pair<DT>(acc[s][0], acc[s][1]);
+                    uint32_t hi = pack_pair<DT>(acc[s][2], acc[s][3]);
                     *reinterpret_cast<uint2*>(yp) = make_uint2(lo, hi);
                 } else {
                     *reinterpret_cast<float4*>(yp) = make_float4(acc[s][0], acc[s][1], acc[s][2], acc[s][3]);

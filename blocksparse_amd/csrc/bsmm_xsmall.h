@@ -11,7 +11,6 @@
 // transposed copy of W, no pre-pass, no workspace.
 #pragma once
 #include "bsmm_common.h"
-#include "bsmm_updat_tr.h"   // ds_tr16
 
 namespace bsmm {
 
@@ -28,7 +27,7 @@ xsmall32_kernel(const typename DT::T* __restrict__ X, const typename DT::T* __re
     static_assert(DT::is16, "small-minibatch kernel: 16-bit storage types");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wave = wave_id();
     const int r = lane & 31, h = lane >> 5;
     const int4 hdr = *reinterpret_cast<const int4*>(lut + 4 * blockIdx.x);
     const int cnt = __builtin_amdgcn_readfirstlane(hdr.y), ob = __builtin_amdgcn_readfirstlane(hdr.z);
@@ -37,9 +36,7 @@ xsmall32_kernel(const typename DT::T* __restrict__ X, const typename DT::T* __re
 
     f32x16 acc[2];
 #pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
+    for (int t = 0; t < 2; ++t) zero_tile(acc[t]);
     // this lane's rows of the activation tile (rows past N are clamped re-reads, never stored)
     const T* xrow[2];
 #pragma unroll
@@ -64,8 +61,7 @@ xsmall32_kernel(const typename DT::T* __restrict__ X, const typename DT::T* __re
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk) {
                 const unsigned char* p = wst + (16 * kk + 8 * h + (t16 >> 2)) * 64 + (16 * (g16 & 1) + 4 * (t16 & 3)) * 2;
-                const uint2 lo = ds_tr16(p), hi = ds_tr16(p + 4 * 64);
-                wq[kk] = make_uint4(lo.x, lo.y, hi.x, hi.y);
+                wq[kk] = ds_tr16_frag(p, 64);
             }
         } else {
 #pragma unroll
@@ -100,8 +96,8 @@ xsmall32_kernel(const typename DT::T* __restrict__ X, const typename DT::T* __re
             s.x += a.x; s.y += a.y; s.z += a.z; s.w += a.w;
         }
         if (n0 + n < N) {
-            const uint32_t lo = (uint32_t)DT::from_f32(s.x) | ((uint32_t)DT::from_f32(s.y) << 16);
-            const uint32_t hi = (uint32_t)DT::from_f32(s.z) | ((uint32_t)DT::from_f32(s.w) << 16);
+            const uint32_t lo = pack_pair<DT>(s.x, s.y);
+            const uint32_t hi = pack_pair<DT>(s.z, s.w);
             *reinterpret_cast<uint2*>(Y + (size_t)(n0 + n) * Kout + ob * 32 + 4 * p) = make_uint2(lo, hi);
         }
     }
@@ -125,7 +121,7 @@ xsmall_narrow_kernel(const typename DT::T* __restrict__ X, const typename DT::T*
     static_assert(DT::is16 && (BS == 16 || BS == 8), "narrow small-minibatch kernel: 16-bit storage types, bsize 16 / 8");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (spelled out: wave_id() changes this kernel's instruction order, profiles/device_prims_isa.md)
     const int g = lane >> 4, t16 = lane & 15;
     const int4 hdr = *reinterpret_cast<const int4*>(lut + 4 * blockIdx.x);
     const int cnt = __builtin_amdgcn_readfirstlane(hdr.y), ob = __builtin_amdgcn_readfirstlane(hdr.z);

@@ -14,7 +14,6 @@
 // Needs N % 8 == 0 (16-byte row pieces), no locks, no gate.
 #pragma once
 #include "bsmm_common.h"
-#include "bsmm_updat_tr.h"   // ds_tr16
 
 namespace bsmm {
 
@@ -32,7 +31,7 @@ xsmall32_a0_kernel(const typename DT::T* __restrict__ X, const typename DT::T* _
     static_assert(DT::is16, "small-minibatch kernel: 16-bit storage types");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wave = wave_id();
     const int r = lane & 31, h = lane >> 5;
     const int4 hdr = *reinterpret_cast<const int4*>(lut + 4 * blockIdx.x);
     const int cnt = __builtin_amdgcn_readfirstlane(hdr.y), ob = __builtin_amdgcn_readfirstlane(hdr.z);
@@ -41,9 +40,7 @@ xsmall32_a0_kernel(const typename DT::T* __restrict__ X, const typename DT::T* _
 
     f32x16 acc[2];
 #pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
+    for (int t = 0; t < 2; ++t) zero_tile(acc[t]);
 
     unsigned char* xst = smem + wave * XS0_PART;           // my X staging: column tile t at t * 2048, [32 rows][64 B]
     unsigned char* wst = xst + 4096;                       // my W staging (fprop): [32 rows][64 B]
@@ -99,18 +96,11 @@ xsmall32_a0_kernel(const typename DT::T* __restrict__ X, const typename DT::T* _
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk) {
                 const unsigned char* p = xst + t * 2048 + 16 * kk * 64 + frag;
-                const uint2 lo = ds_tr16(p), hi = ds_tr16(p + 4 * 64);
-                xf[t][kk] = make_uint4(lo.x, lo.y, hi.x, hi.y);
+                xf[t][kk] = ds_tr16_frag(p, 64);
             }
         if constexpr (TRANSW) {
-            {
-                const uint2 lo = ds_tr16(wst + frag), hi = ds_tr16(wst + frag + 4 * 64);
-                wq0 = make_uint4(lo.x, lo.y, hi.x, hi.y);
-            }
-            {
-                const uint2 lo = ds_tr16(wst + 16 * 64 + frag), hi = ds_tr16(wst + 16 * 64 + frag + 4 * 64);
-                wq1 = make_uint4(lo.x, lo.y, hi.x, hi.y);
-            }
+            wq0 = ds_tr16_frag(wst + frag, 64);
+            wq1 = ds_tr16_frag(wst + 16 * 64 + frag, 64);
         }
         acc[0] = DT::mfma32(wq0, xf[0][0], acc[0]);
         acc[1] = DT::mfma32(wq0, xf[1][0], acc[1]);
@@ -162,7 +152,7 @@ xsmall16_a0_kernel(const typename DT::T* __restrict__ X, const typename DT::T* _
     static_assert(DT::is16, "small-minibatch kernel: 16-bit storage types");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wave = wave_id();
     const int4 hdr = *reinterpret_cast<const int4*>(lut + 4 * blockIdx.x);
     const int cnt = __builtin_amdgcn_readfirstlane(hdr.y), ob = __builtin_amdgcn_readfirstlane(hdr.z);
     const int2* ent = reinterpret_cast<const int2*>(lut) + __builtin_amdgcn_readfirstlane(hdr.x);
@@ -251,7 +241,7 @@ xsmall8_a0_kernel(const typename DT::T* __restrict__ X, const typename DT::T* __
     static_assert(DT::is16, "small-minibatch kernel: 16-bit storage types");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (spelled out: wave_id() changes this kernel's instruction order, profiles/device_prims_isa.md)
     const int4 hdr = *reinterpret_cast<const int4*>(lut + 4 * blockIdx.x);
     const int cnt = __builtin_amdgcn_readfirstlane(hdr.y), ob = __builtin_amdgcn_readfirstlane(hdr.z);
     const int2* ent = reinterpret_cast<const int2*>(lut) + __builtin_amdgcn_readfirstlane(hdr.x);

@@ -17,7 +17,6 @@
 //   nn/tn: M side = output rows, N side = 32 features -> D[row][c], lane = feature c: 128-byte row segments.
 #pragma once
 #include "bsmm_common.h"
-#include "bsmm_updat_tr.h" // ds_tr16
 
 namespace bsmm {
 
@@ -170,8 +169,8 @@ bst_nt_mfma_kernel(const typename TA::T* __restrict__ A, const typename TA::T* _
     auto park = [&](const f32x16& acc) {
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            const uint32_t lo = (uint32_t)TS::from_f32(acc[4 * g + 0]) | ((uint32_t)TS::from_f32(acc[4 * g + 1]) << 16);
-            const uint32_t hi = (uint32_t)TS::from_f32(acc[4 * g + 2]) | ((uint32_t)TS::from_f32(acc[4 * g + 3]) << 16);
+            const uint32_t lo = pack_pair<TS>(acc[4 * g + 0], acc[4 * g + 1]);
+            const uint32_t hi = pack_pair<TS>(acc[4 * g + 2], acc[4 * g + 3]);
             *reinterpret_cast<uint2*>(&olds[r * 64 + ((g ^ ((r >> 2) & 3)) << 4) + 8 * hh]) = make_uint2(lo, hi);
         }
     };
@@ -230,8 +229,8 @@ bst_nt_mfma_kernel(const typename TA::T* __restrict__ A, const typename TA::T* _
         if (pending) flush(pending);                                           // previous tile's scores
         // two independent accumulator chains (even / odd chunks), interleaved instruction by instruction
         f32x16 acc, acc1;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) { acc[i] = 0.f; acc1[i] = 0.f; }
+        zero_tile(acc);
+        zero_tile(acc1);
         if constexpr (SPLIT && !TA::is16) {
             auto split3 = [](const float (&v)[16], uint4 (&p)[3][2]) {          // 16 floats -> 3 pieces x 2 MFMA operands
                 auto pack2 = [](float lo, float hi) { return bf16_pack2(lo, hi); };
@@ -317,8 +316,7 @@ bst_nt_mfma_direct_kernel(const typename TA::T* __restrict__ A, const typename T
     const typename TA::T* qrow = A + ((size_t)n * rows_q + (size_t)qk.x * BS + 32 * ti + r) * state + (size_t)h * hs + 16 * hh;
     const typename TA::T* krow = B + ((size_t)n * rows_k + (size_t)qk.y * BS + 32 * tj + r) * state + (size_t)h * hs + 16 * hh;
     f32x16 acc;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+    zero_tile(acc);
     for (int kc = 0; kc < hs; kc += 32) {
         float fk[16], fq[16];
         load16_f32<TA>(krow + kc, kc + 16 * hh, hs, fk);
@@ -328,8 +326,8 @@ bst_nt_mfma_direct_kernel(const typename TA::T* __restrict__ A, const typename T
     typename TS::T* out = S + (((size_t)n * heads + h) * blocks + b) * (BS * BS) + (size_t)(32 * ti + r) * BS + 32 * tj + 4 * hh;
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-        const uint32_t lo = (uint32_t)TS::from_f32(acc[4 * g + 0]) | ((uint32_t)TS::from_f32(acc[4 * g + 1]) << 16);
-        const uint32_t hi = (uint32_t)TS::from_f32(acc[4 * g + 2]) | ((uint32_t)TS::from_f32(acc[4 * g + 3]) << 16);
+        const uint32_t lo = pack_pair<TS>(acc[4 * g + 0], acc[4 * g + 1]);
+        const uint32_t hi = pack_pair<TS>(acc[4 * g + 2], acc[4 * g + 3]);
         *reinterpret_cast<uint2*>(out + 8 * g) = make_uint2(lo, hi);
     }
 }
@@ -339,27 +337,61 @@ bst_nt_mfma_direct_kernel(const typename TA::T* __restrict__ A, const typename T
 // take every fourth step of the block list (rows of a causal layout have 1 .. nn_max blocks: one wave per tile left the
 // longest rows as a serial chain) and reduce through LDS.  lut = nn_lut / tn_lut (header + entries).
 // ------------------------------------------------------------------------------------------------------------------
+// The output tile of a workgroup and its block list, common to the three MFMA kernels below: workgroup `wid` of (batch entry n, head h),
+// as xcd_head_map deals them (one output tile per workgroup, its 4 waves split the steps); nct = 32-feature tiles per head.  (The map's
+// early return stays in the kernels: returned through a helper it compiled to a second exit block, 28 - 36 bytes more per kernel.)
+template <int BS>
+struct XnTile {
+    int n, h, ct, ts, oc;       // batch entry, head, 32-feature tile, 32-row sub tile of the block, output block
+    const int32_t* hl;          // the head's lut
+    int2 hdr;                   // (first entry, entries) of the output block's list
+    size_t state;               // elements per activation row
+    __device__ __forceinline__ XnTile(const int32_t* __restrict__ lut, int lut_stride, int heads, int hs, int nct, int n_, int h_, int wid)
+        : n(n_), h(h_), ct(wid % nct), ts((wid / nct) % (BS / 32)), oc(wid / (nct * (BS / 32))), hl(lut + (size_t)h_ * lut_stride),
+          hdr(*reinterpret_cast<const int2*>(hl + 2 * oc)), state((size_t)heads * hs) {}
+};
+
+// the four waves' partial tiles meet in LDS; wave w then owns registers 4w .. 4w+3 (rows 8w + {0..3} + 4hh) of the sum and stores them
+// to feature c of the head (lanes with !valid hold a feature past head_state: they take part in the barrier only)
+template <class TO, int BS>
+__device__ __forceinline__ void xn_reduce_store(float (&red)[4][16][64], const f32x16& acc, int wave, int lane, bool valid, const XnTile<BS>& tile,
+                                                typename TO::T* __restrict__ C, int rows_c, int hs, int c) {
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) red[wave][reg][lane] = acc[reg];
+    __syncthreads();
+    if (!valid) return;
+    typename TO::T* out = C + ((size_t)tile.n * rows_c + (size_t)tile.oc * BS + 32 * tile.ts) * tile.state + (size_t)tile.h * hs + c;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int reg = 4 * wave + i;
+        const float v = red[0][reg][lane] + red[1][reg][lane] + red[2][reg][lane] + red[3][reg][lane];
+        const int row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
+        out[(size_t)row * tile.state] = TO::from_f32(v);
+    }
+}
+
 template <class TS, class TB, int BS, bool TRANS>
 __global__ void __launch_bounds__(256)
 bst_xn_mfma_kernel(const typename TS::T* __restrict__ S, const typename TB::T* __restrict__ Bm, typename TB::T* __restrict__ C,
                    const int32_t* __restrict__ lut, int lut_stride, int blocks, int heads, int batch, int hs, int ctx_c, int rows_b, int rows_c) {
     constexpr int SUB = BS / 32;
+    __shared__ float red[4][16][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r = lane & 31, hh = lane >> 5;
     const int nct = (hs + 31) / 32;
     int n, h, wid;
-    if (!xcd_head_map(ctx_c * SUB * nct, heads, batch, n, h, wid)) return;      // one output tile per workgroup, 4 waves split its steps
-    const int ct = wid % nct, ts = (wid / nct) % SUB, oc = wid / (nct * SUB);
-    const int32_t* hl = lut + (size_t)h * lut_stride;
-    const int2 hdr = *reinterpret_cast<const int2*>(hl + 2 * oc);
-    const size_t state = (size_t)heads * hs;
-    const int c = 32 * ct + r;
+    if (!xcd_head_map(ctx_c * SUB * nct, heads, batch, n, h, wid)) return;
+    const XnTile<BS> tile(lut, lut_stride, heads, hs, nct, n, h, wid);
+    const int ts = tile.ts;
+    const int32_t* hl = tile.hl;
+    const int2 hdr = tile.hdr;
+    const size_t state = tile.state;
+    const int c = 32 * tile.ct + r;
     const bool cvalid = c < hs;
     const typename TS::T* sbase = S + ((size_t)n * heads + h) * blocks * (BS * BS);
     const typename TB::T* bcol = Bm + (size_t)n * rows_b * state + (size_t)h * hs + c;
     f32x16 acc;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+    zero_tile(acc);
     // Steps q = (entry, 32-wide slice of the contraction index); the operands of step q+1 are requested before the 16 MFMAs
     // of step q, so a wave's chain over its (up to nn_max) entries is bound by max(load latency, MFMA time) per step instead
     // of their sum (the longest rows set the kernel time: causal layouts have rows of 1 .. nn_max blocks).
@@ -414,20 +446,7 @@ bst_xn_mfma_kernel(const typename TS::T* __restrict__ S, const typename TB::T* _
         if (q + 4 < nsteps) request(q + 4);
         mma32_f32(fa, fb, acc);
     }
-    // the four partial tiles meet in LDS; wave w then owns registers 4w .. 4w+3 (rows 8w + {0..3} + 4hh) of the sum
-    __shared__ float red[4][16][64];
-#pragma unroll
-    for (int reg = 0; reg < 16; ++reg) red[wave][reg][lane] = acc[reg];
-    __syncthreads();
-    if (!cvalid) return;
-    typename TB::T* out = C + ((size_t)n * rows_c + (size_t)oc * BS + 32 * ts) * state + (size_t)h * hs + c;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int reg = 4 * wave + i;
-        const float v = red[0][reg][lane] + red[1][reg][lane] + red[2][reg][lane] + red[3][reg][lane];
-        const int row = (reg & 3) + 8 * (reg >> 2) + 4 * hh;
-        out[(size_t)row * state] = TB::from_f32(v);
-    }
+    xn_reduce_store<TB>(red, acc, wave, lane, cvalid, tile, C, rows_c, hs, c);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -452,17 +471,17 @@ bst_xn_split_kernel(const uint16_t* __restrict__ S, const float* __restrict__ Bm
     const int nct = (hs + 31) / 32;
     int n, h, wid;
     if (!xcd_head_map(ctx_c * SUB * nct, heads, batch, n, h, wid)) return;
-    const int ct = wid % nct, ts = (wid / nct) % SUB, oc = wid / (nct * SUB);
-    const int32_t* hl = lut + (size_t)h * lut_stride;
-    const int2 hdr = *reinterpret_cast<const int2*>(hl + 2 * oc);
-    const size_t state = (size_t)heads * hs;
-    const int c = 32 * ct + r;
+    const XnTile<BS> tile(lut, lut_stride, heads, hs, nct, n, h, wid);
+    const int ts = tile.ts;
+    const int32_t* hl = tile.hl;
+    const int2 hdr = tile.hdr;
+    const size_t state = tile.state;
+    const int c = 32 * tile.ct + r;
     const bool cvalid = c < hs;
     const uint16_t* sbase = S + ((size_t)n * heads + h) * blocks * (BS * BS);
     const float* bcol = Bm + (size_t)n * rows_b * state + (size_t)h * hs + c;
     f32x16 acc;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+    zero_tile(acc);
     uint4 ra[2];                 // score fragment (nn: two contiguous 16-byte loads)
     uint16_t ra1[TRANS ? 16 : 1];
     float rb[16];
@@ -522,18 +541,7 @@ bst_xn_split_kernel(const uint16_t* __restrict__ S, const float* __restrict__ Bm
             acc = DTbf16::mfma32(fa[kk], make_uint4(p1[kk][0], p1[kk][1], p1[kk][2], p1[kk][3]), acc);
         }
     }
-#pragma unroll
-    for (int reg = 0; reg < 16; ++reg) red[wave][reg][lane] = acc[reg];
-    __syncthreads();
-    if (!cvalid) return;
-    float* out = C + ((size_t)n * rows_c + (size_t)oc * BS + 32 * ts) * state + (size_t)h * hs + c;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int reg = 4 * wave + i;
-        const float v = red[0][reg][lane] + red[1][reg][lane] + red[2][reg][lane] + red[3][reg][lane];
-        const int row = (reg & 3) + 8 * (reg >> 2) + 4 * hh;
-        out[(size_t)row * state] = v;
-    }
+    xn_reduce_store<DTf32>(red, acc, wave, lane, cvalid, tile, C, rows_c, hs, c);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -553,15 +561,16 @@ bst_xn_mfma16_kernel(const typename T16::T* __restrict__ S, const typename T16::
     __shared__ __attribute__((aligned(16))) unsigned char tiles[4][2][2][2048];     // [wave][buffer][B tile | S tile]
     __shared__ float red[4][16][64];
     const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wave = wave_id();
     const int r = lane & 31, hh = lane >> 5;
     const int nct = hs / 32;
     int n, h, wid;
     if (!xcd_head_map(ctx_c * SUB * nct, heads, batch, n, h, wid)) return;
-    const int ct = wid % nct, ts = (wid / nct) % SUB, oc = wid / (nct * SUB);
-    const int32_t* hl = lut + (size_t)h * lut_stride;
-    const int2 hdr = *reinterpret_cast<const int2*>(hl + 2 * oc);
-    const size_t state = (size_t)heads * hs;
+    const XnTile<BS> tile(lut, lut_stride, heads, hs, nct, n, h, wid);
+    const int ct = tile.ct, ts = tile.ts;
+    const int32_t* hl = tile.hl;
+    const int2 hdr = tile.hdr;
+    const size_t state = tile.state;
     const T* sbase = S + ((size_t)n * heads + h) * blocks * (BS * BS);
     const T* bbase = Bm + (size_t)n * rows_b * state + (size_t)h * hs + 32 * ct;
     const int drow = lane >> 2, dpiece = lane & 3;                                   // DMA: 16 rows x 64 B per instruction
@@ -569,8 +578,7 @@ bst_xn_mfma16_kernel(const typename T16::T* __restrict__ S, const typename T16::
     const int rd_base = (t16 >> 2) * 64 + (16 * (g16 & 1) + 4 * (t16 & 3)) * 2;      // transposing read, see bsmm_updat_tr.h
     const uint32_t my_lds = lds_addr_of(&tiles[wave][0][0][0]);
     f32x16 acc;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+    zero_tile(acc);
     const int nsteps = hdr.y * SUB;
     uint4 sa[2];                                                                      // nn: score fragment of the step in flight
     auto request = [&](int q, int buf) {
@@ -595,8 +603,7 @@ bst_xn_mfma16_kernel(const typename T16::T* __restrict__ S, const typename T16::
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
             const unsigned char* sp = tile + (16 * kk + 8 * hh) * 64 + rd_base;
-            const uint2 lo = ds_tr16(sp), hi = ds_tr16(sp + 4 * 64);
-            f[kk] = make_uint4(lo.x, lo.y, hi.x, hi.y);
+            f[kk] = ds_tr16_frag(sp, 64);
         }
     };
     if (wave < nsteps) request(wave, 0);
@@ -613,17 +620,7 @@ bst_xn_mfma16_kernel(const typename T16::T* __restrict__ S, const typename T16::
         acc = T16::mfma32(fa[1], fb[1], acc);
         buf ^= 1;
     }
-#pragma unroll
-    for (int reg = 0; reg < 16; ++reg) red[wave][reg][lane] = acc[reg];
-    __syncthreads();
-    T* out = C + ((size_t)n * rows_c + (size_t)oc * BS + 32 * ts) * state + (size_t)h * hs + 32 * ct + r;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int reg = 4 * wave + i;
-        const float v = red[0][reg][lane] + red[1][reg][lane] + red[2][reg][lane] + red[3][reg][lane];
-        const int row = (reg & 3) + 8 * (reg >> 2) + 4 * hh;
-        out[(size_t)row * state] = T16::from_f32(v);
-    }
+    xn_reduce_store<T16>(red, acc, wave, lane, true, tile, C, rows_c, hs, 32 * ct + r);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -910,7 +907,7 @@ bst_nt_softmax_kernel(const typename TA::T* __restrict__ A, const typename TA::T
     __shared__ __attribute__((aligned(16))) unsigned char olds[4][NTS_MAXT][32 * 64];    // per wave: its finished tiles (score type)
     // (row max / row sum of every wave: 256 B at the head of that wave's K buffer, idle by then -- 80 KiB in all: two workgroups per CU)
     const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wave = wave_id();
     const int r = lane & 31, hh = lane >> 5;
     int n, h, Q;
     if (!xcd_head_map(ctx_q, heads, batch, n, h, Q)) return;
@@ -1032,7 +1029,7 @@ bst_nt_softmax_kernel(const typename TA::T* __restrict__ A, const typename TA::T
         if (t + 1 < mine) dma_tile(bbase + (size_t)ent[2 * (wave + 4 * (t + 1)) + 1] * BS * state, a_k);
         f32x16 acc, acc1;
 #pragma unroll
-        for (int i = 0; i < 16; ++i) { acc[i] = 0.f; acc1[i] = 0.f; }
+        for (int i = 0; i < 16; ++i) { acc[i] = 0.f; acc1[i] = 0.f; }   // (one loop over both tiles: two zero_tile() calls order the registers differently)
         if constexpr (SPLIT) {
 #pragma unroll
             for (int c = 0; c < NCH; ++c) {
@@ -1066,8 +1063,8 @@ bst_nt_softmax_kernel(const typename TA::T* __restrict__ A, const typename TA::T
         unsigned char* img = &olds[wave][0][0] + t * 2048;                               // park (bst_nt_mfma_kernel's image of a stored tile)
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            const uint32_t lo = (uint32_t)TS::from_f32(acc[4 * g + 0]) | ((uint32_t)TS::from_f32(acc[4 * g + 1]) << 16);
-            const uint32_t hi = (uint32_t)TS::from_f32(acc[4 * g + 2]) | ((uint32_t)TS::from_f32(acc[4 * g + 3]) << 16);
+            const uint32_t lo = pack_pair<TS>(acc[4 * g + 0], acc[4 * g + 1]);
+            const uint32_t hi = pack_pair<TS>(acc[4 * g + 2], acc[4 * g + 3]);
             *reinterpret_cast<uint2*>(img + r * 64 + ((g ^ ((r >> 2) & 3)) << 4) + 8 * hh) = make_uint2(lo, hi);
         }
     }
