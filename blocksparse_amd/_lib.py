@@ -64,6 +64,7 @@ EMBED_CHUNK = 128
 ENDS_XENT_FWD, ENDS_XENT_BWD, ENDS_EMBED_FWD, ENDS_EMBED_GRAD = 0, 1, 2, 3
 LSTM_SYMBOLS = ("bsmm_lstm_gates", "bsmm_lstm_gates_grad")      # include/bsmm_lstm.h
 BST_SYMBOLS = ("bst_nt", "bst_nn", "bst_tn", "bst_masked_softmax", "bst_softmax_grad", "bst_partial_autoregressive_mask", "bst_nt_softmax", "bst_nt_softmax_grad")
+BST_FLAG_FP32_MFMA = 1   # include/bst.h: fp32 activations on the fp32 matrix-core kernels instead of the three-piece bf16 split (no host class sets it)
 
 
 class BsmmArgs(ctypes.Structure):
