@@ -19,5 +19,6 @@ from . import lstm  # noqa: F401
 from .lstm import fused_lstm_gates  # noqa: F401
 from . import optimize  # noqa: F401
 from .optimize import AdamOptimizer, Ema, PreparedStep, adam_step, ema_step, clip_by_global_norm, global_norm  # noqa: F401
+from .optimize import AdafactorOptimizer, adafactor_step, adafactor_decay  # noqa: F401
 
 __version__ = "0.1.0"

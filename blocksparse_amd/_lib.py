@@ -50,6 +50,7 @@ NORM_MAX, NORM_L2 = 0, 1
 OPTIM_SYMBOLS = ("bsmm_adam", "bsmm_ema", "bsmm_sum_squared", "bsmm_sum_squared_workspace_bytes", "bsmm_clip_norm")      # include/bsmm_optim.h
 OPTIM_LIST_SYMBOLS = ("bsmm_opt_list_bytes", "bsmm_opt_list_build", "bsmm_opt_advance", "bsmm_adam_list", "bsmm_ema_list",
                       "bsmm_sum_squared_list")      # include/bsmm_optim_list.h
+ADAFACTOR_SYMBOLS = ("bsmm_adafactor", "bsmm_adafactor_workspace_bytes")      # include/bsmm_adafactor.h
 NORM_SYMBOLS = ("bsmm_layer_norm", "bsmm_layer_norm_grad", "bsmm_layer_norm_workspace_bytes")      # include/bsmm_norm.h
 EW_SYMBOLS = ("bsmm_bias_act", "bsmm_bias_act_grad", "bsmm_dropout_mask", "bsmm_dropout_apply", "bsmm_bias_act_dropout",
               "bsmm_bias_act_dropout_grad", "bsmm_ew_workspace_bytes")      # include/bsmm_ew.h
@@ -102,6 +103,19 @@ class BsmmAdamArgs(ctypes.Structure):
         ("zero_infs", ctypes.c_int32), ("zero_nans", ctypes.c_int32),
         ("lr", ctypes.c_float), ("lr_new", ctypes.c_float), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float),
         ("epsilon", ctypes.c_float), ("grad_scale", ctypes.c_float), ("clip_sigma", ctypes.c_float), ("saturate", ctypes.c_float),
+    ]
+
+
+class BsmmAdafactorArgs(ctypes.Structure):
+    """Mirror of ``struct bsmm_adafactor_args`` (include/bsmm_adafactor.h)."""
+    _fields_ = [
+        ("param", ctypes.c_void_p), ("cv", ctypes.c_void_p), ("rv", ctypes.c_void_p), ("grad", ctypes.c_void_p),
+        ("param16", ctypes.c_void_p), ("gate", ctypes.c_void_p), ("norm_scale", ctypes.c_void_p), ("workspace", ctypes.c_void_p),
+        ("workspace_bytes", ctypes.c_size_t), ("stream", ctypes.c_void_p), ("rows", ctypes.c_size_t), ("cols", ctypes.c_size_t),
+        ("bsize", ctypes.c_int32), ("grad_dtype", ctypes.c_int32), ("param16_dtype", ctypes.c_int32),
+        ("zero_infs", ctypes.c_int32), ("zero_nans", ctypes.c_int32),
+        ("lr", ctypes.c_float), ("decay", ctypes.c_float), ("epsilon", ctypes.c_float), ("clip_thresh", ctypes.c_float),
+        ("grad_scale", ctypes.c_float), ("saturate", ctypes.c_float),
     ]
 
 
@@ -341,6 +355,11 @@ def load():
         getattr(lib, name).restype = ctypes.c_int
     lib.bsmm_opt_list_bytes.argtypes = [i32]
     lib.bsmm_opt_list_bytes.restype = ctypes.c_size_t
+    # include/bsmm_adafactor.h
+    lib.bsmm_adafactor.argtypes = [ctypes.POINTER(BsmmAdafactorArgs)]
+    lib.bsmm_adafactor.restype = ctypes.c_int
+    lib.bsmm_adafactor_workspace_bytes.argtypes = [ctypes.c_size_t, ctypes.c_size_t, i32]
+    lib.bsmm_adafactor_workspace_bytes.restype = ctypes.c_size_t
     # include/bsmm_norm.h
     pln = ctypes.POINTER(BsmmLnArgs)
     lib.bsmm_layer_norm.argtypes = [vp, vp, vp, vp, vp, vp, pln]

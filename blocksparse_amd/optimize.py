@@ -23,8 +23,18 @@ correction) it was captured with.  The list form (include/bsmm_optim_list.h) lif
     step.run()                                                     # at most 5 launches whatever len(params); capturable
 
 with the step number and the corrected rates on the device, so a captured step follows a schedule.  Its results equal the per-tensor
-calls bit for bit.  Every tensor a call writes gets its version counter bumped (``_lib.wrote``).  PyTorch is plumbing here as everywhere
-in the package; there is no CPU fallback.
+calls bit for bit.
+
+Adafactor (include/bsmm_adafactor.h), the reference's other optimizer (blocksparse/optimize.py:118-191), with factored second moments:
+
+    adafactor_step(w, dw, cv, rv, lr=5e-4, decay=adafactor_decay(t, 0.999), gate=gate, norm_scale=scale, param16=w16)
+    opt = AdafactorOptimizer([w, bias], gated=True, working_dtype=torch.bfloat16);  opt.step(norm_scale=scale)
+
+2-d params keep a row and a column moment, 1-d params one moment per element, block-sparse params a row and a column moment per block
+(2 / bsize of Adam's state) with one update rate over the live blocks.  ``lr`` and ``decay`` are host scalars.
+
+Every tensor a call writes gets its version counter bumped (``_lib.wrote``).  PyTorch is plumbing here as everywhere in the package;
+there is no CPU fallback.
 """
 import ctypes
 import math
@@ -260,6 +270,160 @@ class AdamOptimizer(object):
         for s, new in zip(self.slots, state["slots"]):
             s["Mean"].copy_(new["Mean"])
             s["Var"].copy_(new["Var"])
+        self.steps = int(state["steps"])
+        for p, s in zip(self.params, self.slots):          # the working copies follow the params the caller has loaded
+            if "working" in s:
+                s["working"].copy_(p.detach())
+
+
+def adafactor_step(param, grad, cv, rv=None, lr=5e-4, decay=0.999, epsilon=1e-30, clip_thresh=1.0, grad_scale=1.0, saturate=0.0,
+                   zero_infs=False, zero_nans=False, gate=None, norm_scale=None, param16=None):
+    """One Adafactor step in place on ``param`` (fp32) and its factored second moments from ``grad`` (fp32 / fp16 / bf16); returns
+    ``param``.  The form follows the param's shape: ``[C, K]`` with C > 1 takes ``rv`` [C] and ``cv`` [K]; ``[K]`` or ``[1, K]`` takes
+    ``cv`` [K] alone; ``[blocks, bsize, bsize]`` takes ``rv`` and ``cv`` [blocks, bsize] and, optionally, a ``gate``.  ``decay`` is the
+    value of ``adafactor_decay`` for this call.  See include/bsmm_adafactor.h for the arithmetic and the order of every sum."""
+    _on_device(param, "param")
+    if param.dtype != torch.float32:
+        raise TypeError("param must be float32 (the 16-bit copy the kernels read is param16)")
+    bsize = _bsize_of(param)
+    if bsize:
+        rows, cols, nrv, ncv = param.shape[0], bsize * bsize, param.shape[0] * bsize, param.shape[0] * bsize
+    elif param.dim() == 2 and param.shape[0] > 1:
+        rows, cols, nrv, ncv = param.shape[0], param.shape[1], param.shape[0], param.shape[1]
+    elif param.dim() == 1 or (param.dim() == 2 and param.shape[0] == 1):
+        rows, cols, nrv, ncv = 1, param.numel(), 0, param.numel()
+    else:
+        raise ValueError("only 1 or 2d params are supported")
+    if rows == 0 or cols == 0:
+        raise ValueError("empty param")
+    _like(grad, param, "grad")
+    for t, n, what in ((cv, ncv, "cv"), (rv, nrv, "rv")):
+        if n == 0 and t is None:
+            continue
+        if t is None:
+            raise ValueError("this form needs %s" % what)
+        _on_device(t, what)
+        if t.dtype != torch.float32 or t.device != param.device or (n and t.numel() != n):
+            raise ValueError("%s: expected a contiguous float32 tensor of %d elements on the param's device" % (what, n))
+    if param16 is not None:
+        _like(param16, param, "param16", (torch.float16, torch.bfloat16))
+    lib = _lib.load()
+    need = int(lib.bsmm_adafactor_workspace_bytes(rows, cols, bsize))
+    ws = torch.empty(need // 4, dtype=torch.float32, device=param.device)
+    a = _lib.BsmmAdafactorArgs()
+    a.param, a.cv, a.grad = param.data_ptr(), cv.data_ptr(), grad.data_ptr()
+    a.rv = rv.data_ptr() if rv is not None and nrv else None
+    a.param16 = param16.data_ptr() if param16 is not None else None
+    a.gate = _per_block(gate, param, bsize, "gate")
+    a.norm_scale = _scalar(norm_scale, param, "norm_scale")
+    a.workspace, a.workspace_bytes = ws.data_ptr(), need
+    a.stream = _lib.raw_stream(param.device)
+    a.rows, a.cols, a.bsize = rows, cols, bsize
+    a.grad_dtype = _dtype_code(grad.dtype)
+    a.param16_dtype = _dtype_code(param16.dtype) if param16 is not None else 0
+    a.zero_infs, a.zero_nans = int(bool(zero_infs)), int(bool(zero_nans))
+    a.lr, a.decay, a.epsilon, a.clip_thresh = float(lr), float(decay), float(epsilon), float(clip_thresh)
+    a.grad_scale, a.saturate = float(grad_scale), float(saturate)
+    _lib.check(lib.bsmm_adafactor(ctypes.byref(a)), "bsmm_adafactor")
+    _lib.wrote(param, cv, rv if nrv else None, param16)
+    return param
+
+
+def adafactor_decay(step, beta2, zero_init_variables=False):
+    """The moments' decay for call number ``step`` (1, 2, ...): ``beta2 (1 - beta2^t) / (1 - beta2^(2t))`` from the two accumulators
+    ``decay1_power = beta2^t`` and ``decay2_power = beta2^(2t)`` (blocksparse/optimize.py:131-142).  With ``zero_init_variables`` both
+    start at 0 and stay there: the decay is ``beta2``, the setting for moments that are loaded rather than grown from zero."""
+    if zero_init_variables:
+        return float(beta2)
+    t = max(int(step), 1)
+    return beta2 * (1.0 - beta2 ** t) / (1.0 - beta2 ** (2 * t))
+
+
+class AdafactorOptimizer(object):
+    """Adafactor over a list of fp32 tensors with fp32 ``cv`` / ``rv`` slots (zeros at the start): 2-d params with more than one row
+    keep a row and a column moment, 1-d and ``(1, K)`` params one moment per element, ``[blocks, bsize, bsize]`` params a row and a
+    column moment per block; anything else raises, as the reference does.  ``gated=True`` reads ``param.gate``.  ``working_dtype``:
+    keep a 16-bit copy of every param, rewritten by the step itself (``working_copy(param)``).  The learning rate and the decay are host
+    scalars: a captured step replays with the values it was captured with."""
+
+    def __init__(self, params, learning_rate=5e-4, beta2=0.999, epsilon=1e-30, clip_thresh=1.0, norm_scale=None, grad_scale=1.0, saturate=0.0,
+                 zero_infs=False, zero_nans=False, zero_init_variables=False, gated=False, working_dtype=None):
+        self.params = list(params)
+        if not self.params:
+            raise ValueError("AdafactorOptimizer needs at least one param")
+        self.learning_rate, self.beta2, self.epsilon, self.clip_thresh = float(learning_rate), float(beta2), float(epsilon), float(clip_thresh)
+        self.grad_scale, self.saturate = float(grad_scale), float(saturate)
+        self.zero_infs, self.zero_nans, self.gated, self.zero_init_variables = bool(zero_infs), bool(zero_nans), bool(gated), bool(zero_init_variables)
+        self.norm_scale = norm_scale
+        self.working_dtype = working_dtype
+        self.steps = 0
+        self.slots = []
+        for p in self.params:
+            _on_device(p, "param")
+            if p.dtype != torch.float32:
+                raise TypeError("AdafactorOptimizer keeps fp32 params (working_dtype gives the 16-bit copies)")
+            d = p.detach()
+            bsize = _bsize_of(d)
+            zeros = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=d.device)
+            if bsize:
+                slot = {"cv": zeros(d.shape[0], bsize), "rv": zeros(d.shape[0], bsize)}
+            elif d.dim() == 2 and d.shape[0] > 1:
+                slot = {"cv": zeros(d.shape[1]), "rv": zeros(d.shape[0])}
+            elif d.dim() == 1 or (d.dim() == 2 and d.shape[0] == 1):
+                slot = {"cv": zeros(d.numel())}
+            else:
+                raise ValueError("only 1 or 2d params are supported")
+            if working_dtype is not None:
+                slot["working"] = d.to(working_dtype)
+            self.slots.append(slot)
+
+    def _index(self, param):
+        for i, p in enumerate(self.params):
+            if p is param:
+                return i
+        raise KeyError("not a param of this optimizer")
+
+    def get_slot(self, param, name):
+        """The ``"cv"`` or ``"rv"`` tensor of ``param`` (``None``: the 1-d form keeps no ``rv``)."""
+        return self.slots[self._index(param)].get(name)
+
+    def working_copy(self, param):
+        """The 16-bit copy of ``param`` (``None`` without ``working_dtype``)."""
+        return self.slots[self._index(param)].get("working")
+
+    def current_decay(self):
+        """The decay of the most recent call of ``step``."""
+        return adafactor_decay(self.steps, self.beta2, self.zero_init_variables)
+
+    def step(self, grads=None, norm_scale=None):
+        """One step for every param.  ``grads``: a list parallel to the params (default: ``p.grad``; params without one are left out).
+        ``norm_scale`` overrides the constructor's.  The step counter advances on every call, also when the device skips the step."""
+        self.steps += 1
+        decay = self.current_decay()
+        ns = norm_scale if norm_scale is not None else self.norm_scale
+        if grads is None:
+            grads = [p.grad for p in self.params]
+        grads = list(grads)
+        if len(grads) != len(self.params):
+            raise ValueError("need one gradient (or None) per param")
+        for p, g, slot in zip(self.params, grads, self.slots):
+            if g is None:
+                continue
+            gate = getattr(p, "gate", None) if self.gated and _bsize_of(p) else None
+            adafactor_step(p.detach(), g.detach(), slot["cv"], slot.get("rv"), lr=self.learning_rate, decay=decay, epsilon=self.epsilon,
+                           clip_thresh=self.clip_thresh, grad_scale=self.grad_scale, saturate=self.saturate, zero_infs=self.zero_infs,
+                           zero_nans=self.zero_nans, gate=gate, norm_scale=ns, param16=slot.get("working"))
+
+    def state_dict(self):
+        return {"steps": self.steps, "slots": [{k: s[k].clone() for k in ("cv", "rv") if k in s} for s in self.slots]}
+
+    def load_state_dict(self, state):
+        if len(state["slots"]) != len(self.slots):
+            raise ValueError("state has %d slots, the optimizer %d params" % (len(state["slots"]), len(self.slots)))
+        for s, new in zip(self.slots, state["slots"]):
+            for k in ("cv", "rv"):
+                if k in s:
+                    s[k].copy_(new[k])
         self.steps = int(state["steps"])
         for p, s in zip(self.params, self.slots):          # the working copies follow the params the caller has loaded
             if "working" in s:
