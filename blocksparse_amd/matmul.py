@@ -201,6 +201,7 @@ class BlocksparseMatMul(object):
         self._device_cache = {}
         self._l2_dev = {}
         self._workspaces = {}
+        self._captured_scratch = []       # scratch buffers a captured call was pointed at: held as long as the operator (see _scratch)
         self._args_cache = {}
         self._prepared_w = {}             # op -> (weakref(w), (op, w.data_ptr, w._version, stream), buffer): bsmm_prepare_weights results
         self.cache_prepared = True        # False: prepare on every call (no per-weights cache at all)
@@ -376,11 +377,19 @@ class BlocksparseMatMul(object):
     def _scratch(self, device, stream, tag, slot, need, a=None):
         """Device scratch of at least ``need`` bytes, kept per (device, stream, tag, slot) and grown on demand: the entry points never
         allocate, and consecutive calls on a stream reuse the same bytes in stream order (nothing inside the timed region of a step).
-        ``a``: the argument block to point at it."""
+        ``a``: the argument block to point at it.
+        A buffer handed out while its stream is being captured -- allocated there, or made by an eager warm-up and reused by the capture --
+        has its address baked into the graph's kernel arguments, so it lives as long as the operator (``_captured_scratch``): when a later
+        call outgrows it, the dictionary takes the larger tensor and the old one is still held.  Otherwise the allocator could hand the old
+        bytes to any tensor, and a replay would write into it.  The cost: the list is scanned on every call under capture, and every
+        generation that a capture used stays allocated -- capturing again at a growing minibatch keeps all of them (about 70 MB each for the
+        fp32 weight gradient) until the operator goes."""
         key = (device.index, stream, tag, slot)
         ws = self._workspaces.get(key)
         if ws is None or ws.numel() < need:
             ws = self._workspaces[key] = torch.empty(max(need, 16), dtype=torch.uint8, device=device)
+        if _capturing() and not any(held is ws for held in self._captured_scratch):
+            self._captured_scratch.append(ws)
         if a is not None:
             a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
         return ws
