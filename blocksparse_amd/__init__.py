@@ -17,6 +17,8 @@ from . import xent  # noqa: F401
 from .xent import softmax_cross_entropy  # noqa: F401
 from . import lstm  # noqa: F401
 from .lstm import fused_lstm_gates  # noqa: F401
+from . import select  # noqa: F401
+from .select import rectified_top_k, masked_top_k_softmax, masked_softmax, softmax, sparse_relu, select_path  # noqa: F401
 from . import optimize  # noqa: F401
 from .optimize import AdamOptimizer, Ema, PreparedStep, adam_step, ema_step, clip_by_global_norm, global_norm  # noqa: F401
 from .optimize import AdafactorOptimizer, adafactor_step, adafactor_decay  # noqa: F401

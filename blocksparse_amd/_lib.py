@@ -64,6 +64,10 @@ XENT_SHORT_MAX, XENT_REG_MAX, XENT_WIDE_MAX, XENT_MAX_GRID = 1024, 8192, 32768, 
 EMBED_CHUNK = 128
 ENDS_XENT_FWD, ENDS_XENT_BWD, ENDS_EMBED_FWD, ENDS_EMBED_GRAD = 0, 1, 2, 3
 LSTM_SYMBOLS = ("bsmm_lstm_gates", "bsmm_lstm_gates_grad")      # include/bsmm_lstm.h
+SELECT_SYMBOLS = ("bsmm_select_path", "bsmm_rectified_top_k", "bsmm_masked_top_k_softmax", "bsmm_masked_softmax_grad", "bsmm_sparse_relu",
+                  "bsmm_select_relu_grad")      # include/bsmm_select.h
+SELECT_WAVE8_MAX, SELECT_WAVE16_MAX, SELECT_GROUP2_MAX, SELECT_MAX_K = 512, 1024, 2048, 4096
+SELECT_PATHS = ("wave8", "wave8-wide", "wave16", "wave16-wide", "group2", "group2-wide", "group4", "group4-wide")    # bsmm_select_path's codes
 BST_SYMBOLS = ("bst_nt", "bst_nn", "bst_tn", "bst_masked_softmax", "bst_softmax_grad", "bst_partial_autoregressive_mask", "bst_nt_softmax", "bst_nt_softmax_grad")
 BST_FLAG_FP32_MFMA = 1   # include/bst.h: fp32 activations on the fp32 matrix-core kernels instead of the three-piece bf16 split (no host class sets it)
 
@@ -198,6 +202,14 @@ _lib = None
 
 # Test hook (host side only -- the library itself keeps no switches): flags OR-ed into every call the host classes make.
 #   0 production dispatch, 1 = FLAG_FORCE_VALU, 2 = FLAG_NO_PLAN, 3 = FLAG_FORCE_PLAN, 4 = FLAG_FORCE_MID
+class BsmmSelectArgs(ctypes.Structure):
+    """Mirror of ``struct bsmm_select_args`` (include/bsmm_select.h)."""
+    _fields_ = [
+        ("R", ctypes.c_int32), ("K", ctypes.c_int32), ("k", ctypes.c_int32), ("mask_rows", ctypes.c_int32), ("dtype", ctypes.c_int32),
+        ("rebase", ctypes.c_int32), ("scale", ctypes.c_float), ("alpha", ctypes.c_float), ("stream", ctypes.c_void_p),
+    ]
+
+
 _VARIANT_FLAGS = {0: 0, 1: FLAG_FORCE_VALU, 2: FLAG_NO_PLAN, 3: FLAG_FORCE_PLAN, 4: FLAG_FORCE_MID}
 _call_flags = 0
 _last_kernel = ctypes.c_int32(0)
@@ -396,6 +408,16 @@ def load():
     lib.bsmm_lstm_gates.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, plstm]
     lib.bsmm_lstm_gates_grad.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, plstm]
     for name in LSTM_SYMBOLS:
+        getattr(lib, name).restype = ctypes.c_int
+    # include/bsmm_select.h
+    psel = ctypes.POINTER(BsmmSelectArgs)
+    lib.bsmm_select_path.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
+    lib.bsmm_rectified_top_k.argtypes = [vp, vp, psel]
+    lib.bsmm_masked_top_k_softmax.argtypes = [vp, vp, vp, psel]
+    lib.bsmm_masked_softmax_grad.argtypes = [vp, vp, vp, vp, psel]
+    lib.bsmm_sparse_relu.argtypes = [vp, vp, psel]
+    lib.bsmm_select_relu_grad.argtypes = [vp, vp, vp, psel]
+    for name in SELECT_SYMBOLS:
         getattr(lib, name).restype = ctypes.c_int
     if lib.bsmm_version() != ABI_VERSION:
         raise RuntimeError("blocksparse_amd: %s reports ABI version %d, this binding expects %d -- rebuild the library "

@@ -19,9 +19,9 @@ tensor (fp32, summed in a fixed order).  PyTorch is plumbing (memory, streams, a
 
 ``fused_lstm_gates_test`` / ``fused_lstm_gates_grad_test`` are the NumPy definitions.
 
-Not here: ``split4`` / ``concat4`` (torch views and ``torch.cat``), ``sparse_relu``, ``FusedBasicLSTMCell``, ``grouped_lstm``,
+Not here: ``split4`` / ``concat4`` (torch views and ``torch.cat``), ``FusedBasicLSTMCell``, ``grouped_lstm``,
 ``group_lstm_grads``, gradients in another dtype than the forward's, a second addend fused into the gates, and a bias gradient fused into
-the backward launch.
+the backward launch.  ``sparse_relu`` lives in blocksparse_amd/select.py.
 """
 import ctypes
 
