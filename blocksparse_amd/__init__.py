@@ -19,6 +19,9 @@ from . import lstm  # noqa: F401
 from .lstm import fused_lstm_gates  # noqa: F401
 from . import select  # noqa: F401
 from .select import rectified_top_k, masked_top_k_softmax, masked_softmax, softmax, sparse_relu, select_path  # noqa: F401
+from . import quantize  # noqa: F401  (the operator of the same name stays inside the module: blocksparse_amd.quantize.quantize)
+from .quantize import QuantizeSpec, QuantizeState, log_stats, quantize_fwd, quantize_update_emax, tensor_stats  # noqa: F401
+from .quantize import reset_quantize_states  # noqa: F401
 from . import optimize  # noqa: F401
 from .optimize import AdamOptimizer, Ema, PreparedStep, adam_step, ema_step, clip_by_global_norm, global_norm  # noqa: F401
 from .optimize import AdafactorOptimizer, adafactor_step, adafactor_decay  # noqa: F401

@@ -68,6 +68,9 @@ SELECT_SYMBOLS = ("bsmm_select_path", "bsmm_rectified_top_k", "bsmm_masked_top_k
                   "bsmm_select_relu_grad")      # include/bsmm_select.h
 SELECT_WAVE8_MAX, SELECT_WAVE16_MAX, SELECT_GROUP2_MAX, SELECT_MAX_K = 512, 1024, 2048, 4096
 SELECT_PATHS = ("wave8", "wave8-wide", "wave16", "wave16-wide", "group2", "group2-wide", "group4", "group4-wide")    # bsmm_select_path's codes
+QUANT_SYMBOLS = ("bsmm_quantize", "bsmm_tensor_stats", "bsmm_quant_update_emax", "bsmm_quant_workspace_bytes")      # include/bsmm_quant.h
+QUANT_LANE_ELEMS, QUANT_WG_ELEMS, QUANT_MAX_GRID, QUANT_GROUP = 8, 2048, 2048, 32
+QUANT_NEAREST_AWAY, QUANT_NEAREST_EVEN, QUANT_STOCHASTIC = 0, 1, 2
 BST_SYMBOLS = ("bst_nt", "bst_nn", "bst_tn", "bst_masked_softmax", "bst_softmax_grad", "bst_partial_autoregressive_mask", "bst_nt_softmax", "bst_nt_softmax_grad")
 BST_FLAG_FP32_MFMA = 1   # include/bst.h: fp32 activations on the fp32 matrix-core kernels instead of the three-piece bf16 split (no host class sets it)
 
@@ -207,6 +210,16 @@ class BsmmSelectArgs(ctypes.Structure):
     _fields_ = [
         ("R", ctypes.c_int32), ("K", ctypes.c_int32), ("k", ctypes.c_int32), ("mask_rows", ctypes.c_int32), ("dtype", ctypes.c_int32),
         ("rebase", ctypes.c_int32), ("scale", ctypes.c_float), ("alpha", ctypes.c_float), ("stream", ctypes.c_void_p),
+    ]
+
+
+class BsmmQuantArgs(ctypes.Structure):
+    """Mirror of ``struct bsmm_quant_args`` (include/bsmm_quant.h)."""
+    _fields_ = [
+        ("ebits", ctypes.c_int32), ("fbits", ctypes.c_int32), ("emax", ctypes.c_int32), ("denorm", ctypes.c_int32),
+        ("round_mode", ctypes.c_int32), ("group", ctypes.c_int32), ("bias_pad", ctypes.c_int32), ("stat_mode", ctypes.c_int32),
+        ("dtype", ctypes.c_int32), ("stdv_mul", ctypes.c_float),
+        ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t), ("stream", ctypes.c_void_p),
     ]
 
 
@@ -419,6 +432,15 @@ def load():
     lib.bsmm_select_relu_grad.argtypes = [vp, vp, vp, psel]
     for name in SELECT_SYMBOLS:
         getattr(lib, name).restype = ctypes.c_int
+    # include/bsmm_quant.h
+    pq = ctypes.POINTER(BsmmQuantArgs)
+    lib.bsmm_quantize.argtypes = [vp, vp, vp, vp, ctypes.c_int64, pq]
+    lib.bsmm_tensor_stats.argtypes = [vp, ctypes.c_int64, i32, f32, f32, vp, vp, ctypes.c_size_t, vp]
+    lib.bsmm_quant_update_emax.argtypes = [vp, ctypes.c_int64, pq, vp, vp]
+    for name in QUANT_SYMBOLS:
+        getattr(lib, name).restype = ctypes.c_int
+    lib.bsmm_quant_workspace_bytes.argtypes = [ctypes.c_int64]
+    lib.bsmm_quant_workspace_bytes.restype = ctypes.c_size_t
     if lib.bsmm_version() != ABI_VERSION:
         raise RuntimeError("blocksparse_amd: %s reports ABI version %d, this binding expects %d -- rebuild the library "
                            "(python -c 'import __graft_entry__ as g; g.build()')" % (LIB_PATH, lib.bsmm_version(), ABI_VERSION))

@@ -6,7 +6,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 OUT = os.path.join(_HERE, "libbsmm_hip.so")
-SOURCES = ["bsmm_api.hip", "bst_api.hip", "bsmm_dist.hip", "bsmm_sparsity.hip", "bsmm_optim.hip", "bsmm_optim_list.hip", "bsmm_adafactor.hip", "bsmm_norm.hip", "bsmm_ew.hip", "bsmm_ends.hip", "bsmm_lstm.hip", "bsmm_select.hip"]
+SOURCES = ["bsmm_api.hip", "bst_api.hip", "bsmm_dist.hip", "bsmm_sparsity.hip", "bsmm_optim.hip", "bsmm_optim_list.hip", "bsmm_adafactor.hip", "bsmm_norm.hip", "bsmm_ew.hip", "bsmm_ends.hip", "bsmm_lstm.hip", "bsmm_select.hip", "bsmm_quant.hip"]
 def _headers():
     """every header under csrc/ (a hand-kept list once missed the bench-path kernel: edit it and build() kept the old .so)"""
     return sorted(f for f in os.listdir(CSRC) if f.endswith(".h"))
@@ -16,7 +16,7 @@ def _stale():
     if not os.path.exists(OUT):
         return True
     t = os.path.getmtime(OUT)
-    deps = [os.path.join(CSRC, f) for f in SOURCES + _headers()] + [os.path.join(INCLUDE, h) for h in ("bsmm.h", "bst.h", "bsmm_dist.h", "bsmm_sparsity.h", "bsmm_optim.h", "bsmm_optim_list.h", "bsmm_adafactor.h", "bsmm_norm.h", "bsmm_ew.h", "bsmm_ends.h", "bsmm_lstm.h", "bsmm_select.h")]
+    deps = [os.path.join(CSRC, f) for f in SOURCES + _headers()] + [os.path.join(INCLUDE, h) for h in ("bsmm.h", "bst.h", "bsmm_dist.h", "bsmm_sparsity.h", "bsmm_optim.h", "bsmm_optim_list.h", "bsmm_adafactor.h", "bsmm_norm.h", "bsmm_ew.h", "bsmm_ends.h", "bsmm_lstm.h", "bsmm_select.h", "bsmm_quant.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

@@ -114,4 +114,18 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// ---- the library's one generator (the dropout masks of bsmm_ew_kernels.h, the stochastic rounding of bsmm_quant_kernels.h) ----
+// Philox4x32-10 (Salmon et al., SC'11): counter (c0..c3), key (k0, k1) -> w[0..3]
+__device__ __forceinline__ void ew_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t* w) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t lo0 = 0xD2511F53u * c0, hi0 = __umulhi(0xD2511F53u, c0);
+        const uint32_t lo1 = 0xCD9E8D57u * c2, hi1 = __umulhi(0xCD9E8D57u, c2);
+        const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
+        c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
+}
+
 }  // namespace bsmm
