@@ -201,6 +201,11 @@ int bsmm_gate_weights(const void* W, const float* gate, void* out, int32_t block
     return (int)hipGetLastError();
 }
 
+int bsmm_gated_repair(int op, const void* X, const void* W, void* Y, const bsmm_args* args) {
+    if (op != BSMM_OP_FPROP && op != BSMM_OP_BPROP) return BSMM_ERR_ARG;
+    return gated_repair(op == BSMM_OP_FPROP, X, W, Y, args);
+}
+
 #ifdef X4_TIMELINE
 extern "C" int bsmm_debug_x4_timeline_copy(void* host) { return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(bsmm::g_x4_tl), sizeof(bsmm::g_x4_tl)); }
 #endif

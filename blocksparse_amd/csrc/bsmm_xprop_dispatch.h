@@ -581,6 +581,47 @@ int xprop_typed(bool fprop, const void* X, const void* W, void* Y, const bsmm_ar
     return rc;
 }
 
+// Exactness of a gated call that ran as [bsmm_gate_weights -> the UNGATED kernels] with non-finite activations: a gate-0 block is a zero image
+// there, and the matrix cores multiply it with the live activations -- 0 * Inf = NaN would reach outputs that the in-kernel GATED path
+// (`if (g == 0.f) continue`) and the reference (`if (gate != 0)`, src/blocksparse_hgemm_cn_64_op_gpu.cu:96-100) leave finite.  As on the
+// super-block path (launch_xsuper8): one scan of X leaves a flag in the workspace; when it is set -- never, for a healthy network -- the per-entry
+// V_FMA kernel recomputes Y from W and the gate over the PLAIN table after the matrix-core pass (same stream, Y fully rewritten; no host sync,
+// capturable).  Activations that are not 16-byte aligned are not scanned: the flag is set and Y always recomputed.
+template <class DT, int BS, int AXIS>
+int gated_repair_typed(bool fprop, const void* X, const void* W, void* Y, const bsmm_args* a) {
+    if constexpr (!DT::is16 || BS == 8) return BSMM_ERR_UNSUPPORTED;      // (what bsmm_gate_weights + the ungated call is taken for)
+    else {
+        typedef typename DT::T T;
+        hipStream_t st = static_cast<hipStream_t>(a->stream);
+        int32_t* flag = static_cast<int32_t*>(a->workspace);
+        const bool scan = aligned16(X);
+        if (hipMemsetAsync(flag, scan ? 0 : 1, 16, st) != hipSuccess) return (int)hipGetLastError();
+        if (scan) {
+            const size_t n8 = (size_t)a->N * a->C / 8;                 // (C % 16 == 0: check_common)
+            const int sgrid = (int)std::min<size_t>((n8 + 255) / 256, (size_t)device_cus() * 8);
+            if (a->dtype == BSMM_BF16) nonfinite16_kernel<0x7f80u><<<sgrid, 256, 0, st>>>(static_cast<const uint4*>(X), n8, flag);
+            else                       nonfinite16_kernel<0x7c00u><<<sgrid, 256, 0, st>>>(static_cast<const uint4*>(X), n8, flag);
+        }
+        dim3 grid(a->segments, (a->N + 255) / 256);
+        by_bool(fprop, [&](auto fp) {
+            xprop_valu_kernel<DT, BS, AXIS, decltype(fp)::value><<<grid, 256, 0, st>>>(static_cast<const T*>(X), static_cast<const T*>(W), static_cast<T*>(Y), a->lut,
+                                                                                      a->N, a->C, a->K, a->gate, nullptr, flag);
+        });
+        return (int)hipGetLastError();
+    }
+}
+
+int gated_repair(bool fprop, const void* X, const void* W, void* Y, const bsmm_args* a) {
+    int rc = check_common(a);
+    if (rc) return rc;
+    if (!X || !W || !Y || !a->gate || a->segments <= 0) return BSMM_ERR_ARG;
+    if (a->bsize == 64 || a->locks != 0) return BSMM_ERR_UNSUPPORTED;      // (the repair pass writes Y directly: unlocked tables only)
+    if (!workspace_ok(a, 16)) return BSMM_ERR_WORKSPACE;
+    return with_dtype(a->dtype, [&](auto dt) {
+        return by_shape(a, [&](auto bs, auto ax) { return gated_repair_typed<decltype(dt), decltype(bs)::value, decltype(ax)::value>(fprop, X, W, Y, a); });
+    });
+}
+
 int xprop(bool fprop, const void* X, const void* W, void* Y, const bsmm_args* a);
 
 // bsize 64: the bsize-32 call on the quadrants (b64_inner)

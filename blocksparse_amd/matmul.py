@@ -473,7 +473,7 @@ class BlocksparseMatMul(object):
         """A gated 16-bit fprop / bprop as [bsmm_gate_weights -> the UNGATED call]: the flow / list kernels carry no gate logic (their
         registers are spoken for), and forming g w once per call (6.7 MB at the bench shape, ~3 us) replaces ~80 vector instructions per block
         and row tile inside the staged GATED kernels.  0 / 1 gates: one image, the plain tables (exact); other gates: bf16 two images over the
-        doubled tables, fp16 one image (the reference's rounding).  None = not taken (fp32, bsize 8 / 64, locked tables, short minibatches): the caller runs the GATED kernels."""
+        doubled tables, fp16 one image (the reference's rounding); then ``_gated_repair``, which keeps gate 0 a SKIP for non-finite activations.  None = not taken (fp32, bsize 8 / 64, locked tables, short minibatches): the caller runs the GATED kernels."""
         if not (self.gate_images and gate is not None and x.dtype in (torch.float16, torch.bfloat16) and self.bsize in (16, 32)
                 and self._inner is None and N >= self.GATE_IMAGES_MIN_N[self.bsize]
                 and self._dev_tables["fprop"]["locks"] == 0 and self._dev_tables["bprop"]["locks"] == 0):
@@ -487,7 +487,30 @@ class BlocksparseMatMul(object):
         _lib.check(_lib.load().bsmm_gate_weights(w.data_ptr(), gate.data_ptr(), img.data_ptr(), self.blocks, self.bsize, _dtype_code(w.dtype), pieces, stream),
                    "bsmm_gate_weights")
         op = self if pieces == 1 else self._doubled()
-        return op._xprop(which, x, img, None)
+        out = op._xprop(which, x, img, None)
+        self._gated_repair(which, x, w, gate, out, N)
+        return out
+
+    def _gated_repair(self, which, x, w, gate, out, N):
+        """What keeps [weight images -> the ungated call] a GATED call when the activations hold an Inf / NaN: a gate-0 block is a zero image,
+        and 0 * Inf = NaN would land in outputs that a skipped block leaves finite (the in-kernel GATED path and the reference skip it).
+        bsmm_gated_repair scans ``x`` into a device flag and launches the per-entry gated kernel over the original ``w`` and the plain table,
+        which returns at once when the flag is clear and rewrites ``out`` when it is set: no host sync, capturable, one read of ``x`` and one
+        empty launch for a healthy network."""
+        op, _, feat_in, feat_out, _ = self._XPROP[which]
+        tabs = self._tables_on(x.device)
+        lut_t = getattr(tabs, which)
+        stream = _lib.raw_stream(x.device)
+        key = ("gated_repair", op, N, x.dtype, x.device.index, stream)
+        cached = self._args_cache.get(key)
+        if cached is None:
+            if len(self._args_cache) > 256:
+                self._args_cache.clear()
+            cached = self._args_cache[key] = self._args(lut_t, self._dev_tables[which], N, getattr(self, feat_in), getattr(self, feat_out), x.dtype)
+        a = _lib.BsmmArgs.from_buffer_copy(cached)
+        a.gate = gate.data_ptr()
+        self._scratch(x.device, stream, "gated_repair", 0, 16, a)
+        _lib.check(_lib.load().bsmm_gated_repair(op, x.data_ptr(), w.data_ptr(), out.data_ptr(), ctypes.byref(a)), "bsmm_gated_repair")
 
     # ---- the three passes ------------------------------------------------------------------------
     def _xprop_plan(self, tabs, which, N, n_out_features, dtype, gate):

@@ -225,6 +225,15 @@ int bsmm_gate_grad(void* dw_out, float* dg, const void* dw, const void* W, const
 int bsmm_gate_weights(const void* W, const float* gate, void* out, int32_t blocks, int32_t bsize, int32_t dtype, int32_t pieces,
                       void* stream);
 
+/* Second half of a gated call composed that way, to be issued on the same stream right after the ungated fprop / bprop over the images: a gate-0
+ * block is a ZERO image there, which the matrix cores multiply with the live activations, and 0 * Inf = NaN would reach outputs that a gated call
+ * leaves finite (gate 0 = skipped).  This call scans X for Inf / NaN into a flag in the workspace and launches the per-entry V_FMA kernel over
+ * the ORIGINAL W, gate and lookup table: it returns at once when the flag is clear and rewrites all of Y when it is set.  No host
+ * synchronisation, capturable.  op: BSMM_OP_FPROP / BSMM_OP_BPROP; args as for the gated call itself on the plain table (lut, gate, segments,
+ * blocks, bsize 16 / 32, 16-bit dtype, locks == 0, C / K / N, axis, stream) with a 16-byte aligned workspace of >= 16 bytes.  args->trace is
+ * not written.  A new symbol: BSMM_VERSION is unchanged. */
+int bsmm_gated_repair(int op, const void* X, const void* W, void* Y, const bsmm_args* args);
+
 /* Block-sparse L2 normalisation of W over each output feature (L2NormalizeCK / L2NormalizeGainCK and their gradients,
  * src/blocksparse_l2_norm_op_gpu.cu:396-426,911-934; Python: blocksparse/matmul.py:421-453):
  *   y = gain * x / sqrt(max(sum_sqr, eps)),  sum_sqr[k] = sum of x^2 over the rows of every block in k's column block.

@@ -202,6 +202,22 @@ def test_argument_validation_without_gpu(lib):
     assert L.bsmm_gate_weights(one, None, one, 4, 32, lib.BF16, 1, None) == -1            # (round 6) gated weight images: arguments, then support
     assert L.bsmm_gate_weights(one, one, one, 4, 32, lib.F32, 1, None) == -2
     assert L.bsmm_gate_weights(one, one, one, 4, 32, lib.BF16, 3, None) == -2
+    # the repair pass of a gated call over weight images: arguments, support (16-bit, bsize 16 / 32, unlocked tables), then its flag's 16 bytes
+    a.blocks, a.bsize, a.dtype, a.axis, a.plan, a.plan_magic, a.gate, a.locks = 4, 32, lib.BF16, 1, None, 0, 256, 0
+    assert L.bsmm_gated_repair(lib.OP_UPDAT, one, one, one, ctypes.byref(a)) == -1
+    assert L.bsmm_gated_repair(lib.OP_FPROP, one, one, None, ctypes.byref(a)) == -1
+    a.gate = None
+    assert L.bsmm_gated_repair(lib.OP_FPROP, one, one, one, ctypes.byref(a)) == -1
+    a.gate, a.locks = 256, 1
+    assert L.bsmm_gated_repair(lib.OP_BPROP, one, one, one, ctypes.byref(a)) == -2
+    a.locks, a.workspace, a.workspace_bytes = 0, None, 0
+    assert L.bsmm_gated_repair(lib.OP_BPROP, one, one, one, ctypes.byref(a)) == -3
+    a.workspace, a.workspace_bytes = 264, 16
+    assert L.bsmm_gated_repair(lib.OP_BPROP, one, one, one, ctypes.byref(a)) == -3
+    a.workspace, a.dtype = 256, lib.F32
+    assert L.bsmm_gated_repair(lib.OP_FPROP, one, one, one, ctypes.byref(a)) == -2
+    a.dtype, a.bsize, a.C, a.K = lib.F16, 8, 64, 64
+    assert L.bsmm_gated_repair(lib.OP_FPROP, one, one, one, ctypes.byref(a)) == -2
 
 
 def test_short_workspace_is_refused_before_anything_is_enqueued(lib):

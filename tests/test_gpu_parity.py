@@ -493,7 +493,10 @@ def test_inf_in_an_unconnected_feature_does_not_reach_the_output(env, bs, axis):
     zero-filled 32x32 super-blocks, where 0 * Inf WOULD appear: the call scans the activations for non-finite values and, when
     there is one, recomputes the output with the per-entry kernel after the matrix-core pass (round 4; bsmm_super8.h) -- checked
     here on the super-block path itself (FORCE_PLAN, BSMM_K_XPROP_SUPER8 asserted), with an Inf, with a NaN, and with clean inputs
-    (whose result must be the matrix-core one: identical to a second clean call)."""
+    (whose result must be the matrix-core one: identical to a second clean call).
+    This test poisons a whole feature block for every row, in bf16, on the forced plan kernels; tests/test_containment_gpu.py has the single
+    poisoned elements (whose row or column must stay clean elsewhere), the other types and every other route -- V_FMA, per-segment, small-minibatch,
+    mid, fp32 split, 128-row flow units, the bsize-16 pair kernel, bsize 64, locked tables, gated calls -- with the masks of tests/_containment.py."""
     torch, BSMM, lib = env
     rng = np.random.default_rng(3 + bs + axis)
     CB = KB = 48 if bs != 8 else 64
