@@ -71,6 +71,28 @@ struct DTbf16 {
 
 __device__ __forceinline__ uint4 zero_u4() { return make_uint4(0u, 0u, 0u, 0u); }
 
+// ------------------------------------------------------------------------------------------------
+// The epilogue of every gated weight-gradient kernel:  DW = alpha * gate[w] * sum + beta * DW, rounded once -- where gate[w] == 0 means that
+// the block's sum is NOT USED, whatever it holds (the reference skips such a block: blocksparse/matmul.py:416-418 `if gate[w] != 0.0`,
+// src/blocksparse_hgemm_cn_64_op_gpu.cu:737-739,874-875 `if (gate != 0.0f) {...} else if (!accumulate) zero`).  A product 0 * sum would store
+// NaN into a switched-off block as soon as one Inf or NaN reached its sum.  So a gate-0 block gets +0 (beta == 0: DW is not read) or
+// beta * DW; for every other gate, and without a gate, the arithmetic is alpha * gate[w] (one product) times the sum, as it always was.
+// gw: the block the gate belongs to (the 64 x 64 block's when the kernel works on its quadrants).
+// ------------------------------------------------------------------------------------------------
+struct DwGate { float a; bool live; };
+__device__ __forceinline__ DwGate dw_gate(float alpha, const float* __restrict__ gate, size_t gw) {
+    if (!gate) return DwGate{alpha, true};
+    const float g = gate[gw];
+    return DwGate{g != 0.f ? alpha * g : 0.f, g != 0.f};
+}
+__device__ __forceinline__ float dw_term(DwGate g, float sum) { return g.a * (g.live ? sum : 0.f); }
+template <class DT>
+__device__ __forceinline__ void dw_store(typename DT::T* dst, DwGate g, float sum, float beta) {
+    float out = dw_term(g, sum);
+    if (beta != 0.f) out += beta * DT::to_f32(*dst);
+    *dst = DT::from_f32(out);
+}
+
 // gather 8 16-bit elements p[0], p[stride], ... into one 16-byte register group (element j in bits 16*(j&1) of word j/2)
 __device__ __forceinline__ uint4 gather8_u16(const uint16_t* p, size_t stride) {
     uint32_t e[8];

@@ -60,8 +60,11 @@ dw_shard_finalize_kernel(const float* __restrict__ sums, const void* __restrict_
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         if (i + e >= n) break;
-        const float a = gate ? alpha * gate[(i0 + i + e) / bsq] : alpha;
-        float v = a * sums[i + e];
+        // (this file's own copy of the gated epilogue, bsmm_common.h::dw_term: a block whose gate is 0 does not use its sum)
+        const float g = gate ? gate[(i0 + i + e) / bsq] : 1.f;
+        const bool live = !gate || g != 0.f;
+        const float a = gate ? (live ? alpha * g : 0.f) : alpha;
+        float v = a * (live ? sums[i + e] : 0.f);
         if constexpr (T16 == 0) {
             if (beta != 0.f) v += beta * static_cast<const float*>(dw_old)[i + e];
             static_cast<float*>(out)[i + e] = v;

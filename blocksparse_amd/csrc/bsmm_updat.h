@@ -37,7 +37,7 @@ updat32_kernel(PtrList8 Xs, PtrList8 Es, typename DT::T* __restrict__ DW, const 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r = lane & 31, h = lane >> 5;
     const int c = lut[2 * w], k = lut[2 * w + 1];
-    if (gate) alpha *= gate[w];                       // gated dw (updat_test(dw_gated=True), blocksparse/matmul.py:412-418)
+    const DwGate dg = dw_gate(alpha, gate, w);        // gated dw (updat_test(dw_gated=True), blocksparse/matmul.py:412-418): gate 0 = the sum is not used
 
     f32x16 acc;
     zero_tile(acc);
@@ -67,9 +67,7 @@ updat32_kernel(PtrList8 Xs, PtrList8 Es, typename DT::T* __restrict__ DW, const 
         const int reg = slot >> 6, ln = slot & 63;
         const int ci = (reg & 3) + 8 * (reg >> 2) + 4 * (ln >> 5), ko = ln & 31;
         const size_t idx = (size_t)w * 1024 + ci * 32 + ko;
-        float out = alpha * sum;
-        if (beta != 0.f) out += beta * DT::to_f32(DW[idx]);
-        DW[idx] = DT::from_f32(out);
+        dw_store<DT>(DW + idx, dg, sum, beta);
     }
 }
 
@@ -88,7 +86,7 @@ updat16_kernel(PtrList8 Xs, PtrList8 Es, typename DT::T* __restrict__ DW, const 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r = lane & 15, q = lane >> 4;
     const int c = lut[2 * w], k = lut[2 * w + 1];
-    if (gate) alpha *= gate[w];                       // gated dw (updat_test(dw_gated=True), blocksparse/matmul.py:412-418)
+    const DwGate dg = dw_gate(alpha, gate, w);        // gated dw (updat_test(dw_gated=True), blocksparse/matmul.py:412-418): gate 0 = the sum is not used
 
     f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int p = 0; p < pcount; ++p) {
@@ -123,9 +121,7 @@ updat16_kernel(PtrList8 Xs, PtrList8 Es, typename DT::T* __restrict__ DW, const 
         const int reg = slot >> 6, ln = slot & 63;
         const int ci = 4 * (ln >> 4) + reg, ko = ln & 15;
         const size_t idx = (size_t)w * 256 + ci * 16 + ko;
-        float out = alpha * sum;
-        if (beta != 0.f) out += beta * DT::to_f32(DW[idx]);
-        DW[idx] = DT::from_f32(out);
+        dw_store<DT>(DW + idx, dg, sum, beta);
     }
 }
 
@@ -150,7 +146,7 @@ updat_valu_kernel(PtrList8 Xs, PtrList8 Es, typename DT::T* __restrict__ DW, con
 
     const int w = blockIdx.x;
     const int c = lut[2 * w], k = lut[2 * w + 1];
-    if (gate) alpha *= gate[w];                       // gated dw (updat_test(dw_gated=True), blocksparse/matmul.py:412-418)
+    const DwGate dg = dw_gate(alpha, gate, w);        // gated dw (updat_test(dw_gated=True), blocksparse/matmul.py:412-418): gate 0 = the sum is not used
     const int tid = threadIdx.x;
     const int slice = (SL == 1) ? 0 : tid / OUTS;
     const int obase = (SL == 1) ? tid : tid % OUTS;
@@ -204,17 +200,13 @@ updat_valu_kernel(PtrList8 Xs, PtrList8 Es, typename DT::T* __restrict__ DW, con
 #pragma unroll
             for (int j = 0; j < SL; ++j) s += red[j * OUTS + tid];
             const size_t idx = (size_t)w * OUTS + tid;
-            float out = alpha * s;
-            if (beta != 0.f) out += beta * DT::to_f32(DW[idx]);
-            DW[idx] = DT::from_f32(out);
+            dw_store<DT>(DW + idx, dg, s, beta);
         }
     } else {
 #pragma unroll
         for (int j = 0; j < PER; ++j) {
             const size_t idx = (size_t)w * OUTS + obase + j * 256;
-            float out = alpha * acc[j];
-            if (beta != 0.f) out += beta * DT::to_f32(DW[idx]);
-            DW[idx] = DT::from_f32(out);
+            dw_store<DT>(DW + idx, dg, acc[j], beta);
         }
     }
 }
@@ -317,15 +309,10 @@ updat8_a0_pairs_kernel(PtrList8 Xs, PtrList8 Es, typename DT::T* __restrict__ DW
     // D[m][col]: col = t16, rows m = 4 g + i.  Block 0 = (m < 8, col < 8), block 1 = (m >= 8, col >= 8): lane (g, t16) holds a diagonal quadrant iff
     // (g >> 1) == (t16 >> 3); its block is the one it loaded for (w).
     if (have && (g >> 1) == (t16 >> 3)) {
-        const float a = gate ? alpha * gate[w] : alpha;
+        const DwGate dg = dw_gate(alpha, gate, w);
         T* out = DW + (size_t)w * 64 + (t16 & 7);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int ci = 4 * (g & 1) + i;
-            float v = a * acc[i];
-            if (beta != 0.f) v += beta * DT::to_f32(out[ci * 8]);
-            out[ci * 8] = DT::from_f32(v);
-        }
+        for (int i = 0; i < 4; ++i) dw_store<DT>(out + (4 * (g & 1) + i) * 8, dg, acc[i], beta);
     }
 }
 
@@ -343,7 +330,7 @@ updat_a0_wave_kernel(PtrList8 Xs, PtrList8 Es, typename DT::T* __restrict__ DW, 
     const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (w >= blocks) return;
     const int c = lut[2 * w], k = lut[2 * w + 1];
-    const float a_eff = gate ? alpha * gate[w] : alpha;
+    const DwGate dg = dw_gate(alpha, gate, w);
     if constexpr (BS == 32) {
         const int r = lane & 31, h = lane >> 5;                  // A[m = ci][k = n]: lane (ci = r, K half h) holds columns 16 s + 8 h ..
         f32x16 acc;
@@ -364,9 +351,7 @@ updat_a0_wave_kernel(PtrList8 Xs, PtrList8 Es, typename DT::T* __restrict__ DW, 
         for (int reg = 0; reg < 16; ++reg) {
             const int ci = (reg & 3) + 8 * (reg >> 2) + 4 * h;
             const size_t idx = (size_t)w * 1024 + ci * 32 + r;
-            float out = a_eff * acc[reg];
-            if (beta != 0.f) out += beta * DT::to_f32(DW[idx]);
-            DW[idx] = DT::from_f32(out);
+            dw_store<DT>(DW + idx, dg, acc[reg], beta);
         }
     } else {
         const int t16 = lane & 15, g = lane >> 4;                // v_mfma_f32_16x16x32: lane (row t16, K group g) holds columns 32 s + 8 g ..
@@ -385,9 +370,7 @@ updat_a0_wave_kernel(PtrList8 Xs, PtrList8 Es, typename DT::T* __restrict__ DW, 
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const size_t idx = (size_t)w * 256 + (4 * g + i) * 16 + t16;
-            float out = a_eff * acc[i];
-            if (beta != 0.f) out += beta * DT::to_f32(DW[idx]);
-            DW[idx] = DT::from_f32(out);
+            dw_store<DT>(DW + idx, dg, acc[i], beta);
         }
     }
 }

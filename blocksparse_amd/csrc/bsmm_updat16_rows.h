@@ -23,7 +23,7 @@
 //   epilogue:   the 16 x 16 sums of a block go to DW (split = 1: alpha / beta here, one rounding) or into the part's own fp32 image in the
 //               workspace, and updat16_rows_finalize_kernel adds the images and rounds once (deterministic: no atomics -- fp32 atomics into
 //               one image cost 6 us per part at BASELINE configs[2]).
-// N % 8 == 0 and 16-byte aligned operands (row pieces of 16 bytes); a ragged last chunk re-reads the last 8 entries and zeroes the X pieces.
+// N % 8 == 0 and 16-byte aligned operands (row pieces of 16 bytes); a ragged last chunk re-reads the last 8 entries and zeroes the X and the DY pieces.
 //
 // Measured (profiles/r05_updat16_rows_*.txt): BASELINE configs[2] 88-92 us against 115-125 for the windowed kernel; 4096^2 20 % 138 against 241;
 // 8192^2 5 % 292 against 481.  Cycle stamps: the data of a chunk (128 KiB per CU) takes 1.8 us = 30 B/clk/CU, what every L2 -> CU stream of
@@ -201,8 +201,10 @@ updat16_rows_kernel(PtrList8 Xs, PtrList8 Es, typename DT::T* __restrict__ DW, f
         // a chunk: per K-step the blocks in groups of four -- four B fragments requested together, then four MFMAs.  The A fragment is the
         // wave's row slot of the block: blocks are sorted by slot, so `a` changes once per K-step (at e0: a real branch -- the empty asm
         // keeps hipcc from turning it into selects per block).  Slots past nb multiply leftovers into accumulators nobody stores.
-        auto compute = [&](int pos) {
+        auto compute = [&](int pos, int qq) {
             const unsigned char* slot = smem + pos * G::SLAB;
+            const bool tail = qq * 64 + 64 > N;      // ragged last chunk: the DY pieces past N are re-reads of the last 8 entries -- zeroed like the X pieces
+                                                     // (a zero X against the copy of an Inf / NaN in DY would be NaN)
             if (U6_NO_MATH) {
                 if (U6_NO_MATH == 2) { __builtin_amdgcn_s_sleep(24); __builtin_amdgcn_s_sleep(24); }      // ~3000 cycles asleep instead of the matrix work
                 if (x[0][0].x == 0x12345u && x[1][1].y == 77u) acc[0][0] += 1.f;
@@ -218,6 +220,10 @@ updat16_rows_kernel(PtrList8 Xs, PtrList8 Es, typename DT::T* __restrict__ DW, f
                         uint4 b[4];
 #pragma unroll
                         for (int t = 0; t < 4; ++t) b[t] = U6_NO_BREAD ? make_uint4(koff[4 * g + t], 1u, 2u, 3u) : *reinterpret_cast<const uint4*>(sl + koff[4 * g + t]);
+                        if (tail && !(qq * 64 + 32 * ks + 8 * q < N)) {
+#pragma unroll
+                            for (int t = 0; t < 4; ++t) b[t] = zero_u4();
+                        }
 #pragma unroll
                         for (int t = 0; t < 4; ++t) {
                             const int jj = 4 * g + t;
@@ -246,7 +252,7 @@ updat16_rows_kernel(PtrList8 Xs, PtrList8 Es, typename DT::T* __restrict__ DW, f
             shuffle(qq);
             if (qq + 1 < q_end) { load_x(qq + 1); issue(qq + 1, pos ^ 1); }
             U6_STAMP(0)
-            compute(pos);
+            compute(pos, qq);
             U6_STAMP(3)
             __syncthreads();
             U6_STAMP(4)
@@ -301,8 +307,8 @@ updat16_rows_finalize_kernel(const float* __restrict__ scratch, typename DT::T* 
         const float4 t = *reinterpret_cast<const float4*>(scratch + (size_t)part * nel + i);
         s.x += t.x; s.y += t.y; s.z += t.z; s.w += t.w;
     }
-    const float a = gate ? alpha * gate[i >> 8] : alpha;
-    float v[4] = {a * s.x, a * s.y, a * s.z, a * s.w};
+    const DwGate dg = dw_gate(alpha, gate, i >> 8);              // (gate 0: the sum is not used, bsmm_common.h)
+    float v[4] = {dw_term(dg, s.x), dw_term(dg, s.y), dw_term(dg, s.z), dw_term(dg, s.w)};
     if (beta != 0.f) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] += beta * DT::to_f32(DW[i + e]);

@@ -81,15 +81,17 @@ updat32_a1_tr_kernel(PtrList8 Xs, PtrList8 Es, typename DT::T* __restrict__ DW, 
                 a[kk] = ds_tr16_frag(sp, 64);
                 b[kk] = ds_tr16_frag(sp + 2048, 64);
             }
-            if (n0 + 32 > N) {   // ragged tail: rows >= N were clamped re-reads -> zero their contribution (A side suffices)
+            if (n0 + 32 > N) {   // ragged tail: rows >= N were clamped re-reads -> zero them on BOTH sides (a zero against the copy of an Inf / NaN in row N - 1 is NaN)
 #pragma unroll
                 for (int kk = 0; kk < 2; ++kk) {
                     const int nb = n0 + 16 * kk + 8 * h;   // K index j of this lane's fragment is row nb + j
                     uint32_t* u = reinterpret_cast<uint32_t*>(&a[kk]);
+                    uint32_t* v = reinterpret_cast<uint32_t*>(&b[kk]);
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         const uint32_t lo = (nb + 2 * j < N) ? 0xffffu : 0u, hi = (nb + 2 * j + 1 < N) ? 0xffff0000u : 0u;
                         u[j] &= (lo | hi);
+                        v[j] &= (lo | hi);
                     }
                 }
             }
@@ -184,15 +186,17 @@ updat32_a1_small_kernel(PtrList8 Xs, PtrList8 Es, typename DT::T* __restrict__ D
                 a[kk] = ds_tr16_frag(sp, 64);
                 b[kk] = ds_tr16_frag(sp + 2048, 64);
             }
-            if (n0 + 32 > N) {   // ragged tail: rows >= N were clamped re-reads -> zero their contribution (A side suffices)
+            if (n0 + 32 > N) {   // ragged tail: rows >= N were clamped re-reads -> zero them on BOTH sides (a zero against the copy of an Inf / NaN in row N - 1 is NaN)
 #pragma unroll
                 for (int kk = 0; kk < 2; ++kk) {
                     const int nb = n0 + 16 * kk + 8 * h;
                     uint32_t* u = reinterpret_cast<uint32_t*>(&a[kk]);
+                    uint32_t* v = reinterpret_cast<uint32_t*>(&b[kk]);
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         const uint32_t lo = (nb + 2 * j < N) ? 0xffffu : 0u, hi = (nb + 2 * j + 1 < N) ? 0xffff0000u : 0u;
                         u[j] &= (lo | hi);
+                        v[j] &= (lo | hi);
                     }
                 }
             }
@@ -202,15 +206,13 @@ updat32_a1_small_kernel(PtrList8 Xs, PtrList8 Es, typename DT::T* __restrict__ D
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the clamped tail prefetch, before the next pair re-primes the ring
     }
     // D[ci][ko]: col = ko = lane & 31, row ci = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
-    const float a_eff = gate ? alpha * gate[q64 ? w >> 2 : w] : alpha;
+    const DwGate dg = dw_gate(alpha, gate, q64 ? w >> 2 : w);      // (gate 0: the sum is not used, bsmm_common.h)
 #pragma unroll
     for (int reg = 0; reg < 16; ++reg) {
         const int ci = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
         const size_t idx = q64 ? (size_t)(w >> 2) * 4096 + (size_t)(32 * ((w >> 1) & 1) + ci) * 64 + 32 * (w & 1) + (lane & 31)
                                : (size_t)w * 1024 + ci * 32 + (lane & 31);
-        float out = a_eff * acc[reg];
-        if (beta != 0.f) out += beta * DT::to_f32(DW[idx]);
-        DW[idx] = DT::from_f32(out);
+        dw_store<DT>(DW + idx, dg, acc[reg], beta);
     }
 }
 
@@ -262,14 +264,16 @@ updat16_a1_tr_kernel(PtrList8 Xs, PtrList8 Es, typename DT::T* __restrict__ DW, 
             wr_pos = (wr_pos + 1) & (UT16_D - 1);
             const int n0 = (wave + 4 * qq) * 32;
             uint4 a = ds_tr16_frag(slot + rd_base, 32);
-            const uint4 b = ds_tr16_frag(slot + 1024 + rd_base, 32);
-            if (n0 + 32 > N) {
+            uint4 b = ds_tr16_frag(slot + 1024 + rd_base, 32);
+            if (n0 + 32 > N) {   // ragged tail: the clamped re-reads are zeroed on BOTH sides (a zero against the copy of an Inf / NaN in row N - 1 is NaN)
                 const int nb = n0 + 8 * q;
                 uint32_t* u = reinterpret_cast<uint32_t*>(&a);
+                uint32_t* v = reinterpret_cast<uint32_t*>(&b);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const uint32_t lo = (nb + 2 * e < N) ? 0xffffu : 0u, hi = (nb + 2 * e + 1 < N) ? 0xffff0000u : 0u;
                     u[e] &= (lo | hi);
+                    v[e] &= (lo | hi);
                 }
             }
             acc = DT::mfma16(a, b, acc);

@@ -124,12 +124,17 @@ __device__ __forceinline__ void u2_direct_block(const PtrList8& Xs, const PtrLis
             rd_pos = (rd_pos + 1 == D) ? 0 : rd_pos + 1;
             wr_pos = (wr_pos + 1 == D) ? 0 : wr_pos + 1;
             uint4 a = ds_tr16_frag(sp, 64);
-            const uint4 b = ds_tr16_frag(sp + 1024, 64);
+            uint4 b = ds_tr16_frag(sp + 1024, 64);
             const int nb = (first + U2_WAVES * j) * 16 + 8 * h;      // K index i of this lane's fragment is row nb + i
-            if (nb + 8 > N) {                                        // ragged tail: rows >= N were clamped re-reads
+            if (nb + 8 > N) {                                        // ragged tail: rows >= N were clamped re-reads -- zeroed on BOTH sides (0 x the copy of an Inf is NaN)
                 uint32_t* u = reinterpret_cast<uint32_t*>(&a);
+                uint32_t* v = reinterpret_cast<uint32_t*>(&b);
 #pragma unroll
-                for (int i = 0; i < 4; ++i) u[i] &= ((nb + 2 * i < N) ? 0xffffu : 0u) | ((nb + 2 * i + 1 < N) ? 0xffff0000u : 0u);
+                for (int i = 0; i < 4; ++i) {
+                    const uint32_t m = ((nb + 2 * i < N) ? 0xffffu : 0u) | ((nb + 2 * i + 1 < N) ? 0xffff0000u : 0u);
+                    u[i] &= m;
+                    v[i] &= m;
+                }
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // (the next request may overwrite this slot only after the reads returned)
             acc = DT::mfma32(a, b, acc);
@@ -662,18 +667,14 @@ updat2_reduce_kernel(const float* __restrict__ parts, typename DT::T* __restrict
 #pragma unroll
             for (int e = 0; e < 4; ++e) sums[o + e * ostep] = r[e];
         } else {
-            const float a = gate ? alpha * gate[q64 ? w >> 2 : w] : alpha;
+            const DwGate dg = dw_gate(alpha, gate, q64 ? w >> 2 : w);      // (gate 0: the sum is not used, bsmm_common.h)
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float v = a * r[e];
-                if (beta != 0.f) v += beta * DT::to_f32(DW[o + e * ostep]);
-                DW[o + e * ostep] = DT::from_f32(v);
-            }
+            for (int e = 0; e < 4; ++e) dw_store<DT>(DW + o + e * ostep, dg, r[e], beta);
         }
     }
 }
 
-// DW[w] = alpha * gate[w] * scratch[w] + beta * DW[w], rounded once (second pass of the scratch path; gate may be NULL)
+// DW[w] = alpha * gate[w] * scratch[w] + beta * DW[w], rounded once (second pass of the scratch path; gate may be NULL; gate 0: beta * DW[w])
 template <class DT>
 __global__ void __launch_bounds__(256)
 updat_finalize_gated_kernel(const float* __restrict__ scratch, typename DT::T* __restrict__ DW, size_t n, int bsq, float alpha, float beta,
@@ -681,8 +682,8 @@ updat_finalize_gated_kernel(const float* __restrict__ scratch, typename DT::T* _
     const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
     if (i >= n || (skip_if && skip_if[0] != 0)) return;      // (skip_if: the fp32 split paths' non-finite flag -- their repair pass writes DW then)
     const float4 s = *reinterpret_cast<const float4*>(scratch + i);
-    const float a = gate ? alpha * gate[i / bsq] : alpha;
-    float v[4] = {a * s.x, a * s.y, a * s.z, a * s.w};
+    const DwGate dg = dw_gate(alpha, gate, i / bsq);              // (gate 0: the sum is not used, bsmm_common.h)
+    float v[4] = {dw_term(dg, s.x), dw_term(dg, s.y), dw_term(dg, s.z), dw_term(dg, s.w)};
     if (beta != 0.f) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] += beta * DT::to_f32(DW[i + e]);

@@ -181,11 +181,14 @@ updat16_win_kernel(PtrList8 Xs, PtrList8 Es, typename DT::T* __restrict__ DW, fl
                         const int nb = n0 + 32 * ks + 8 * q;
 #pragma unroll
                         for (int j = 0; j < NS; ++j) {
+                            // (both sides: a zero against the clamped copy of an Inf / NaN in the last row is NaN)
                             uint32_t* u = reinterpret_cast<uint32_t*>(&a[j]);
+                            uint32_t* v = reinterpret_cast<uint32_t*>(&b[j]);
 #pragma unroll
                             for (int e = 0; e < 4; ++e) {
                                 const uint32_t lo = (nb + 2 * e < N) ? 0xffffu : 0u, hi = (nb + 2 * e + 1 < N) ? 0xffff0000u : 0u;
                                 u[e] &= (lo | hi);
+                                v[e] &= (lo | hi);
                             }
                         }
                     }

@@ -573,7 +573,8 @@ class BlocksparseMatMul(object):
         """DW = alpha * sum_p updat(X_p, DY_p) + beta * DW  (ops BlocksparseMatmulDW / ...DWA).
 
         ``xs``/``dys``: one tensor each or equally long lists of up to 8 tensors (the reference's Plist).
-        ``gate``: gated dw (op attr gated_dw): the sum of block w is scaled by gate[w].
+        ``gate``: gated dw (op attr gated_dw): the sum of block w is scaled by gate[w]; a block whose gate is 0 is skipped, as in the
+        reference -- it gets beta * DW (zeros with beta == 0) whatever x and dy hold, an Inf or NaN included.
         ``sums_only``: return the raw fp32 sums [blocks, bs, bs] (a view of the call's workspace, valid until the next updat on
         this stream with the same ``slot``) instead of DW -- the data-parallel path reduces them over the ranks in fp32
         (``dist.DwReduce``) or calls ``updat_finalize``; only the streaming kernel (bsize 32: 16-bit types on either feature axis, fp32 on

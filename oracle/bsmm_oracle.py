@@ -228,7 +228,7 @@ def bprop(t, E, W, axis, gate=None):
 def updat(t, Is, Es, axis, alpha=1.0, beta=0.0, dw_in=None, gate=None):
     """DW[w] = alpha * sum_p X_p[c] DY_p[k]^T + beta * DW_in[w]   (matmul.py:401-419; kernel
     semantics for alpha/beta/pairs: src/blocksparse_matmul_op_gpu.cu:2684-2814,2865).  gate (with dw_gated=True in the
-    reference, matmul.py:412-418): the sum of block w is scaled by gate[w]."""
+    reference, matmul.py:412-418): the sum of block w is scaled by gate[w]; a block whose gate is 0 is skipped."""
     bs, CB, KB = t["bsize"], t["CB"], t["KB"]
     if isinstance(Is, np.ndarray):
         Is, Es = [Is], [Es]
@@ -247,7 +247,11 @@ def updat(t, Is, Es, axis, alpha=1.0, beta=0.0, dw_in=None, gate=None):
             for w, (c, k) in enumerate(t["updat_list"]):
                 U[w] += X[c] @ D[k].T
     if gate is not None:
-        U *= np.asarray(gate, dtype=np.float64)[:, None, None]
+        # a block whose gate is 0 is SKIPPED, not multiplied (matmul.py:416-418 `if gate[w] != 0.0`): its sum is not used, whatever it
+        # holds -- 0 * Inf would leave NaN in a switched-off block.  (gate_grad below multiplies, as the reference's does.)
+        g = np.asarray(gate, dtype=np.float64)
+        with np.errstate(invalid="ignore"):
+            U = np.where((g != 0.0)[:, None, None], U * g[:, None, None], 0.0)
     U *= alpha
     if beta != 0.0:
         U += beta * np.asarray(dw_in, dtype=np.float64)
